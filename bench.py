@@ -11,10 +11,16 @@ One "step" = one replay of the whole device-resident batch: the replay kernels o
 batch's slice classes (C2: k_replay_fast; C3-C5: k_replay_cls and its k_replay_reg retry
 passes, the PAR slices, the general kernel for what fits no other) + k_tables + k_finalize.
 Inputs are uploaded before the timed region; host SoA packing and H2D time are
-reported separately.  The CPU baseline is the CPU restatement (oracle/) run with one
-task per workflow on the host's cores over a bounded sample.
+reported separately.  A plain run sets up, warms up, times the K steps and prints the
+result line.  --full adds everything measured or checked beside the headline, after the
+timed steps: the CPU baseline (the CPU restatement, oracle/, run with one task per
+workflow on the host's cores over a bounded sample), the full-size GPU == oracle parity
+check, the refreshTasks / row-encoder kernels, the drop-in host path and the stream-copy
+ceiling (each has a --no-* switch).  --dump-outputs DIR writes the last timed step's
+output records as DIR/<table>.npy (dump_outputs).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--wfs M] [--config C]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--wfs M] [--config C] [--full]
+       [--dump-outputs DIR]
        (N>1: torchrun --nproc-per-node N bench.py --gpus N ...)
 Other lines: --long-stride 125000 (configs[3]: histories at the 204,800-event count limit
 mixed in), --tasks (with the stateBuilder task lists), --carry (replay onto a loaded
@@ -356,6 +362,57 @@ def parity_check(db, ctx, stream, config, mine, seed, long_stride=0):
             "oracle_status": hist, "cpu_threads": threads, "seconds": time.perf_counter() - t0,
             "method": "per-entry digest of the persisted projection (cdr_entry_digests_async vs "
                       "oracle/digest_ref.cpp), CopyToPersistence mutableStateBuilder.go:257-270"}
+
+
+DUMP_BUDGET = 60 * 10 ** 6  # bytes --dump-outputs may write, all files together
+DUMP_SEED = 0x5EED0D07
+
+
+def dump_outputs(dirpath, db, ctx, stream):
+    """--dump-outputs: the caller's output buffers (cdr_out) as the last timed step left
+    them, one DIR/<table>.npy per table that has rows, plus the per-entry digests of those buffers
+    (cdr_entry_digests_async) as entry_digest.npy, which cover every byte of every entry.
+    The records are integer structs: a file holds a (rows, 32-bit words per row) float64
+    array, each little-endian word of a record as one exact value.  The smallest tables are
+    written whole; a table larger than its share of DUMP_BUDGET is a sample of its rows,
+    ascending, drawn from DUMP_SEED and the table's row count alone, so two builds run
+    with the same arguments write the same rows."""
+    torch, info, tot = db.torch, db.info, db.info.totals
+    n = info.n_entries
+    rows = {"result": (n, abi.CdrWfResult), "exec": (n, abi.CdrExecInfo), "repl": (n, abi.CdrReplState),
+            "vh": (tot.vh, abi.CdrVHItem), "act": (tot.act, abi.CdrActivityInfo),
+            "timer": (tot.timer, abi.CdrTimerInfo), "child": (tot.child, abi.CdrChildInfo),
+            "cancel": (tot.cancel, abi.CdrCancelInfo), "signal": (tot.signal, abi.CdrSignalInfo),
+            "rp": (tot.rp, abi.CdrResetPoint), "sa": (tot.sa, abi.CdrKV),
+            "transfer": (tot.xfer, abi.CdrTask), "timer_tasks": (tot.ttask, abi.CdrTask)}
+    # (a table the workload leaves without rows, e.g. C2's pending timers, gets no file)
+    tables = [(k, t, int(rows[k][0]), C.sizeof(rows[k][1])) for k, t in db.out_t.items() if k in rows and rows[k][0]]
+    if "n_tasks" in db.out_t:
+        tables.append(("n_tasks", db.out_t["n_tasks"], n, 8))
+    per = torch.zeros(max(1, n), dtype=torch.int64, device="cuda")
+    dsum = torch.zeros(1, dtype=torch.int64, device="cuda")
+    rc = abi.lib().cdr_entry_digests_async(ctx, C.byref(db.db), C.byref(db.out), C.c_void_p(per.data_ptr()),
+                                           C.c_void_p(dsum.data_ptr()), C.c_void_p(stream))
+    if rc:
+        raise RuntimeError(f"cdr_entry_digests_async rc={rc}")
+    torch.cuda.synchronize()
+    tables.append(("entry_digest", per.view(torch.uint8), n, 8))
+    os.makedirs(dirpath, exist_ok=True)
+    left = DUMP_BUDGET
+    tables.sort(key=lambda t: t[2] * t[3])
+    for i, (name, t, nrows, rowb) in enumerate(tables):
+        assert rowb % 4 == 0 and nrows * rowb <= t.numel(), name
+        # a row of `rowb` bytes becomes rowb / 4 float64 values; 128 B for the .npy header
+        keep = min(nrows, max(1, max(0, left // (len(tables) - i) - 128) // (2 * rowb)))
+        a = t[: nrows * rowb].view(nrows, rowb)
+        if keep < nrows:
+            pick = np.sort(np.random.default_rng([DUMP_SEED, nrows]).choice(nrows, keep, replace=False))
+            a = a[torch.from_numpy(pick).to(a.device)]
+        words = a.cpu().numpy().view("<u4").astype(np.float64)
+        path = os.path.join(dirpath, name + ".npy")
+        np.save(path, words)
+        left -= os.path.getsize(path)
+        log(f"dumped {name}: {keep} of {nrows} rows x {rowb // 4} words")
 
 
 def compare_task_lists(got, nt, caps_g, ref, caps_r, ne):
@@ -943,17 +1000,17 @@ def main():
     ap.add_argument("--wfs", type=int, default=1_000_000, help="workflows per GPU")
     ap.add_argument("--config", type=int, default=2)
     ap.add_argument("--seed", type=int, default=0x5EED0002)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-stream-peak", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-stream-peak", action="store_true", help="--full without the stream-copy ceiling")
     ap.add_argument("--no-fast-path", action="store_true", help="replay every slice with the general kernel")
     ap.add_argument("--no-wave", action="store_true", help="no wave slices: divergent histories in lane slices")
     ap.add_argument("--wave-all", action="store_true", help="every divergent history on a wave slice")
-    ap.add_argument("--no-refresh", action="store_true", help="skip the refreshTasks / row-encoder side measurements")
+    ap.add_argument("--no-refresh", action="store_true", help="--full without the refreshTasks / row-encoder side measurements")
     ap.add_argument("--no-host-path", action="store_true",
-                    help="skip the drop-in host path measurement (decoded histories -> cdr_replay_batch)")
+                    help="--full without the drop-in host path measurement (decoded histories -> cdr_replay_batch)")
     ap.add_argument("--host-path-wfs", type=int, default=200000,
                     help="workflows of the host-path sample (the population's first ones)")
-    ap.add_argument("--no-parity", action="store_true", help="skip the full-size GPU == oracle digest check")
+    ap.add_argument("--no-parity", action="store_true", help="--full without the full-size GPU == oracle digest check")
     ap.add_argument("--no-par", action="store_true",
                     help="long register-table histories on wave slices instead of CDR_SLICE_PAR slices")
     ap.add_argument("--no-cls", action="store_true",
@@ -975,7 +1032,22 @@ def main():
     ap.add_argument("--carry", action="store_true",
                     help="carry-in line: each history's second half replayed onto its first half's loaded state "
                          "(--config, --wfs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every side measurement and check: the CPU baseline, the "
+                         "GPU == oracle parity check, the refreshTasks / row-encoder kernels, the drop-in host path "
+                         "and the stream-copy ceiling (the --no-* options switch single ones off); without it a run "
+                         "sets up, warms up, times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write what the last step left in the caller's output buffers "
+                         "(cdr_out) as DIR/<table>.npy: float64, one value per 32-bit word, a fixed seeded sample "
+                         f"of rows where a table is large ({DUMP_BUDGET // 10 ** 6} MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.ndc_forks or args.carry):
+        ap.error("--dump-outputs writes the headline line's outputs (not with --ndc-forks / --carry)")
+    if not args.full:  # a plain run: none of the side legs, in any of the three lines
+        args.no_cpu_baseline = args.no_stream_peak = args.no_refresh = args.no_host_path = args.no_parity = True
     import torch  # before libcdr.so: torch's HIP runtime must be the process's one (tests/conftest.py)
     L = abi.lib()
     if L.cdr_build_flags():  # a profiling / tuning variant never reaches a reported line
@@ -1049,6 +1121,8 @@ def main():
     n = C.c_uint32(args.steps)
     L.cdr_timing_read(ctx, ms, C.byref(n))
     kern_ms = float(np.mean(np.frombuffer(ms, np.float32)[: n.value]))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, db, ctx, stream)
 
     # verification + the only collective: RCCL allreduce of counters and checksums
     res = db.results()

@@ -25,9 +25,9 @@ export TMPDIR=/tmp
 sha1sum cadence_amd/libcdr.so > "$out/lib_sha1"
 B="timeout -k 10"
 
-bench_line() {  # name limit args...
+bench_line() {  # name limit args...  (--full: the line with its CPU baseline, parity check and side measurements)
   local name=$1 lim=$2; shift 2
-  $B "$lim" python -u bench.py "$@" > "$out/$name.json" 2> "$out/$name.log" || { tail -20 "$out/$name.log"; return 1; }
+  $B "$lim" python -u bench.py --full "$@" >"$out/$name.json" 2> "$out/$name.log" || { tail -20 "$out/$name.log"; return 1; }
   tail -c 400 "$out/$name.json"; echo
 }
 
@@ -94,10 +94,10 @@ EOF
   multirank)
     export CDR_BENCH_BACKEND=gloo
     $B 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 \
-      bench.py --gpus 2 --wfs 300000 --steps 5 --warmup 2 --no-cpu-baseline --no-refresh --no-stream-peak \
+      bench.py --gpus 2 --wfs 300000 --steps 5 --warmup 2 --full --no-cpu-baseline --no-refresh --no-stream-peak \
       > "$out/c2_n2.json" 2> "$out/c2_n2.log" || exit 1
     $B 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29512 \
-      bench.py --gpus 4 --config 4 --wfs 100000 --steps 3 --warmup 1 --no-cpu-baseline --no-refresh --no-stream-peak \
+      bench.py --gpus 4 --config 4 --wfs 100000 --steps 3 --warmup 1 --full --no-cpu-baseline --no-refresh --no-stream-peak \
       > "$out/c4_n4.json" 2> "$out/c4_n4.log" || exit 1 ;;
   ingest)
     for c in 2 3 5; do
