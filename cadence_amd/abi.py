@@ -228,6 +228,14 @@ TASK_TYPES = {0: "DecisionTask", 1: "ActivityTask", 2: "CloseExecution", 3: "Can
               19: "WorkflowTimeout", 20: "DeleteHistoryEvent", 22: "WorkflowBackoffTimer"}
 CdrCarry = _S("cdr_carry", [("src", C.c_void_p), ("caps", C.c_void_p), ("n_src", u32), ("_pad", u32),
                             ("totals", CdrTotals), ("state", CdrOut), ("in_memory", C.c_void_p)])
+# WorkflowMutation of a carry-in replay (schema.h cdr_mut_info / cdr_mutation)
+MUT_OK, MUT_NOT_OK, MUT_E_ORDER = range(3)
+MUT_SNAPSHOT = 0x1
+CdrMutInfo = _S("cdr_mut_info", [("code", i32), ("flags", u32), ("condition", i64), ("n_del_act", u32),
+                                 ("n_del_timer", u32), ("n_del_child", u32), ("n_del_cancel", u32),
+                                 ("n_del_signal", u32), ("_pad", u32)])
+CdrMutation = _S("cdr_mutation", [("upsert", CdrOut)] + [(n, C.c_void_p) for n in (
+    "del_act", "del_timer", "del_child", "del_cancel", "del_signal", "info")])
 CdrSlices = _S("cdr_slices", [
     ("n_slices", u32), ("_pad", u32), ("n_rows", u64), ("arena_words", u64)] + [(n, C.c_void_p) for n in (
         "slice_row0", "slice_len", "lane_wf", "slab", "arena", "slice_scratch_off", "slice_act_slots",
@@ -323,6 +331,7 @@ MIRRORS = {
     "cdr_task": CdrTask, "cdr_vh_token": CdrVHToken, "cdr_vh_branch": CdrVHBranch, "cdr_vhs": CdrVHS,
     "cdr_ndc_task": CdrNdcTask, "cdr_ndc_decision": CdrNdcDecision, "cdr_ndc_round": CdrNdcRound, "cdr_last_decision": CdrLastDecision,
     "cdr_opts": CdrOpts, "cdr_ingest_in": CdrIngestIn, "cdr_ingest_out": CdrIngestOut,
+    "cdr_mut_info": CdrMutInfo, "cdr_mutation": CdrMutation,
 }
 
 # C ABI entry points declared in include/cdr/cdr.h and include/cdr/synth.h
@@ -364,6 +373,10 @@ EXPORTS = {
     "cdr_encode_cql_async": (i32, [C.c_void_p, i32, C.POINTER(CdrDevBatch), C.POINTER(CdrOut),
                                      C.POINTER(CdrStrtab), C.c_void_p, C.c_void_p, u64, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
+    "cdr_mutation_async": (i32, [C.c_void_p, C.POINTER(CdrDevBatch), C.POINTER(CdrOut), C.POINTER(CdrMutation),
+                                 C.c_void_p]),
+    "cdr_mutation_batch": (i32, [C.c_void_p, C.POINTER(CdrBatch), C.POINTER(CdrWfCaps), C.POINTER(CdrTotals),
+                                 C.POINTER(CdrOut), C.POINTER(CdrMutation), C.c_void_p]),
     "cdr_plan_class_ranges": (i32, [C.c_void_p, u32, C.c_void_p, C.c_void_p]),
     "cdr_compact_async": (i32, [C.c_void_p, i32, C.POINTER(CdrDevBatch), C.POINTER(CdrOut), C.c_void_p,
                                 C.c_void_p, C.c_void_p]),

@@ -47,6 +47,9 @@ enum cdr_ws_slot {
   WS_RETRY,  // the class kernels' retry lists: 8 counters, then a list of n_slices per class
   WS_TSTAGE, WS_THEAD,  // k_replay_cls<TASKS>: staged task records, per-entry headers (k_tasks_merge)
   WS_CLS_MAP,  // the device class sort's per-event (class, position), type word and annotation (k_cls_count -> k_cls_gather)
+  // cdr_mutation_batch (mutation.hip): the mutation's device buffers (the states reuse WS_CY_* / WS_O_*)
+  WS_MUT_RESULT, WS_MUT_ACT, WS_MUT_TIMER, WS_MUT_CHILD, WS_MUT_CANCEL, WS_MUT_SIGNAL, WS_MUT_DEL_ACT,
+  WS_MUT_DEL_TIMER, WS_MUT_DEL_CHILD, WS_MUT_DEL_CANCEL, WS_MUT_DEL_SIGNAL, WS_MUT_INFO,
   WS_NUM
 };
 

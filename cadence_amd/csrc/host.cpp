@@ -1202,6 +1202,8 @@ uint64_t cdr_struct_size(const char* name) {
       {"cdr_ndc_task", sizeof(cdr_ndc_task)},
       {"cdr_ndc_decision", sizeof(cdr_ndc_decision)},
       {"cdr_ndc_round", sizeof(cdr_ndc_round)},
+      {"cdr_mut_info", sizeof(cdr_mut_info)},
+      {"cdr_mutation", sizeof(cdr_mutation)},
   };
   for (const E& e : table)
     if (std::strcmp(e.n, name) == 0) return e.s;

@@ -348,6 +348,66 @@ class Outputs:
         return [self.tables[table][off + j] for j in range(n)]
 
 
+MUT_TABLES = ("act", "timer", "child", "cancel", "signal")
+
+
+class Mutation:
+    """The WorkflowMutation of a carry-in replay (cdr_mutation, schema.h): what
+    CloseTransactionAsMutation hands to UpdateWorkflowExecution, as the net difference of
+    the loaded states (batch.carry) and the replayed ones (`out`).
+
+    ``upsert`` is an Outputs with `out`'s plan: its result counts and pending tables hold the
+    rows to upsert (compacted, ascending keys); exec / repl / vh / rp / sa alias `out`'s
+    records, which are always written whole — so ``Engine.encode_rows`` / ``encode_blobs``
+    take it as it is.  ``info[w]`` is entry w's cdr_mut_info (code, flags, condition, delete
+    counts) and ``deleted(w, table)`` its delete keys.  `fill`: the byte every buffer the
+    call writes into is pre-filled with (tests: what the call leaves untouched)."""
+
+    def __init__(self, batch: Batch, out: "Outputs", fill: int = 0):
+        pl = out.plan
+        n = max(1, batch.n_wfs)
+        self.carry = batch.carry
+        ct = batch.carry.state.plan.totals if batch.carry is not None else abi.CdrTotals()
+        up = Outputs.__new__(Outputs)
+        up.n_wfs, up.plan, up.tasks = batch.n_wfs, pl, None
+        up.result = (abi.CdrWfResult * n)()
+        up.exec, up.repl, up.last_decision = out.exec, out.repl, out.last_decision
+        up.tables = dict(out.tables)
+        for t in MUT_TABLES:
+            up.tables[t] = (TABLE_TYPES[t] * max(1, getattr(pl.totals, t)))()
+        self.upsert = up
+        self.info = (abi.CdrMutInfo * n)()
+        self.dels = {t: (C.c_int64 * max(1, getattr(ct, t)))() for t in MUT_TABLES}
+        if fill:
+            for b in self.buffers():
+                C.memset(b, fill, C.sizeof(b))
+
+    def buffers(self) -> list:
+        """Every buffer the call writes, in cdr_mutation's order."""
+        return [self.upsert.result] + [self.upsert.tables[t] for t in MUT_TABLES] + \
+            [self.dels[t] for t in MUT_TABLES] + [self.info]
+
+    def raw(self) -> bytes:
+        return b"".join(_bytes(b) for b in self.buffers())
+
+    def cstruct(self) -> abi.CdrMutation:
+        m = abi.CdrMutation()
+        m.upsert = self.upsert.cstruct()
+        for t in MUT_TABLES:
+            setattr(m, "del_" + t, C.addressof(self.dels[t]))
+        m.info = C.addressof(self.info)
+        self._keep = m
+        return m
+
+    def deleted(self, w: int, table: str) -> list:
+        """Entry w's delete keys of `table` ("act", "timer", "child", "cancel", "signal")."""
+        n = getattr(self.info[w], "n_del_" + table)
+        if n == 0:
+            return []
+        off = getattr(self.carry.state.plan.caps[int(self.carry.src[w])], table + "_off")
+        return [int(self.dels[table][off + j]) for j in range(n)]
+
+
 _hip_lib = None
 
 
@@ -599,6 +659,72 @@ class Engine:
                     got[r] = raw[int(offs[r]):int(offs[r + 1])]
                     codes[r] = int(stat[r])
             return got, codes
+        finally:
+            for p in ptrs:
+                hip.hipFree(p)
+
+    def mutation(self, batch: Batch, out: Outputs, fill: int = 0, via: str = "batch") -> Mutation:
+        """The WorkflowMutation of carry-in batch `batch` replayed into `out` (by this engine
+        or the oracle): through cdr_mutation_batch (host buffers, the default) or, with
+        via="async", through cdr_mutation_async on device copies made with the HIP runtime —
+        the same kernel either way."""
+        mut = Mutation(batch, out, fill)
+        L = abi.lib()
+        pl = out.plan
+        if via == "batch":
+            rc = L.cdr_mutation_batch(self.ctx, C.byref(batch.cstruct()), pl.caps, C.byref(pl.totals),
+                                      C.byref(out.cstruct()), C.byref(mut.cstruct()), None)
+            if rc:
+                raise RuntimeError(f"cdr_mutation_batch rc={rc}")
+            return mut
+        hip = _hip()
+        ptrs = []
+
+        def up(x, nb=None):
+            nb = C.sizeof(x) if nb is None else nb
+            p = C.c_void_p()
+            if hip.hipMalloc(C.byref(p), C.c_size_t(max(8, nb))) != 0:
+                raise RuntimeError("hipMalloc failed")
+            ptrs.append(p)
+            if nb and hip.hipMemcpy(p, x if isinstance(x, int) else C.addressof(x), C.c_size_t(nb), 1) != 0:
+                raise RuntimeError("hipMemcpy H2D failed")
+            return p.value
+        try:
+            db = abi.CdrDevBatch()
+            db.n_wfs = batch.n_wfs
+            db.caps = up(pl.caps)
+            cy = batch.carry
+            if cy is not None:
+                st = cy.state
+                hc = cy.cstruct()
+                dc = abi.CdrCarry(n_src=hc.n_src, totals=hc.totals)
+                dc.src = up(cy.src.ctypes.data, cy.src.nbytes)
+                dc.caps = up(st.plan.caps)
+                dc.state.result, dc.state.exec = up(st.result), up(st.exec)
+                for t in MUT_TABLES:
+                    setattr(dc.state, t, up(st.tables[t]))
+                if cy.in_memory is not None:
+                    dc.in_memory = up(cy.in_memory.ctypes.data, cy.in_memory.nbytes)
+                db.carry = up(dc)
+            o = abi.CdrOut()
+            o.result = up(out.result)
+            for t in MUT_TABLES:
+                setattr(o, t, up(out.tables[t]))
+            bufs = mut.buffers()
+            dev = [up(b) for b in bufs]
+            m = abi.CdrMutation()
+            m.upsert.result = dev[0]
+            for k, t in enumerate(MUT_TABLES):
+                setattr(m.upsert, t, dev[1 + k])
+                setattr(m, "del_" + t, dev[6 + k])
+            m.info = dev[11]
+            rc = L.cdr_mutation_async(self.ctx, C.byref(db), C.byref(o), C.byref(m), None)
+            if rc:
+                raise RuntimeError(f"cdr_mutation_async rc={rc}")
+            for b, d in zip(bufs, dev):
+                if hip.hipMemcpy(C.addressof(b), d, C.c_size_t(C.sizeof(b)), 2) != 0:  # synchronises
+                    raise RuntimeError("hipMemcpy D2H failed")
+            return mut
         finally:
             for p in ptrs:
                 hip.hipFree(p)

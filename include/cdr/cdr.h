@@ -633,6 +633,40 @@ int cdr_encode_cql_async(cdr_ctx* ctx, int table, const cdr_dev_batch* in, const
                          const cdr_strtab* strs, const cdr_exec_persist* persist, const uint32_t* cluster_names,
                          uint64_t n_rows, uint64_t* row_off, uint8_t* values, int32_t* row_status, void* stream);
 
+/* The WorkflowMutation of a carry-in replay (schema.h cdr_mutation; mutation.hip): run after
+ * cdr_replay_sliced_async on the same `in` / `out` (same stream).  This is the step after the
+ * replay in nDCHistoryReplicator.applyNonStartEventsToCurrentBranch and the 2DC
+ * historyReplicator: transactionMgr.updateWorkflow -> CloseTransactionAsMutation
+ * (service/history/mutableStateBuilder.go:3721-3785) -> UpdateWorkflowExecution, which writes
+ * the execution row, per pending table the rows to upsert and the keys to delete, and
+ * Condition = nextEventIDInDB.  The call diffs, per entry and table, the loaded rows
+ * (in->carry) against the replayed rows (out) by key and writes the net mutation into `mut`:
+ * upserts compacted in mut->upsert — a cdr_out the row encoders (cdr_encode_rows_async,
+ * cdr_encode_blobs_async, cdr_encode_cql_async) take as it is — delete keys and the per-entry
+ * cdr_mut_info.  Nothing is written for rows past an entry's counts; an entry whose replay is
+ * not CDR_OK gets only its info record and a copy of its result.
+ * Preconditions: both states' pending tables in ascending, unique key order (every replay
+ * path writes them so); the kernel checks the order as it merges — an entry that violates it
+ * gets CDR_MUT_E_ORDER and zero counts (its own upsert / delete slices are then unspecified,
+ * other entries are unaffected).  Timer keys are string handles: equal timer IDs must have
+ * equal handles in the loaded state and in the batch (the replay kernels need the same).
+ * Capacities: the delete arrays are sized by in->carry->totals and the upsert tables by the
+ * totals of in->caps; delete counts cannot exceed the loaded row counts nor upsert counts
+ * OUT's, so nothing can overflow.
+ * One launch, no allocation, no host round trip; asynchronous on `stream`.  CDR_API_EINVAL
+ * for null arguments and for in->carry == NULL (a batch without loaded states has no
+ * mutation: everything it writes is a snapshot). */
+int cdr_mutation_async(cdr_ctx* ctx, const cdr_dev_batch* in, const cdr_out* out, const cdr_mutation* mut,
+                       void* stream);
+/* The same for host buffers (as cdr_rebuild_batch): `b->carry` (the loaded states), `caps` /
+ * `totals` of the replayed batch and `out` (its replay's outputs) are uploaded into the
+ * context's grow-only workspace together with the current contents of `mut`'s buffers, the
+ * kernel runs, and `mut`'s buffers are downloaded (bytes the kernel leaves untouched keep the
+ * caller's values).  Only b->n_wfs and b->carry are read from `b`.  Synchronous on `stream`;
+ * one call at a time per context. */
+int cdr_mutation_batch(cdr_ctx* ctx, const cdr_batch* b, const cdr_wf_caps* caps, const cdr_totals* totals,
+                       const cdr_out* out, cdr_mutation* mut, void* stream);
+
 /* Stream compaction of the per-workflow pending tables into dense tables
  * (device pointers): for each table, rows [caps.off, caps.off + result.n) of every
  * workflow are copied to dense[row_base[w] ...]; row_base is an exclusive scan of

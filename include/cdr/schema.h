@@ -696,6 +696,49 @@ typedef struct cdr_carry {
   const uint8_t* in_memory;
 } cdr_carry;
 
+/* WorkflowMutation of a carry-in replay (cdr_mutation_async, cdr.h): what
+ * CloseTransactionAsMutation (mutableStateBuilder.go:3721-3785) hands to
+ * UpdateWorkflowExecution, as the NET difference between the loaded state IN (record
+ * carry.src[w] of carry.state) and the replayed state OUT (entry w of the replay's cdr_out).
+ * Keys: activity schedule_id, timer timer_id (the string handle), child / cancel / signal
+ * initiated_id.  Per table, an OUT row is upserted when its key is absent from IN or its
+ * record differs from IN's row with that key in any byte; an IN key absent from OUT is
+ * deleted; condition = IN.exec.next_event_id. */
+enum { CDR_MUT_OK = 0, CDR_MUT_NOT_OK = 1, CDR_MUT_E_ORDER = 2 };
+/* no stored predecessor (carry.src[w] < 0, or carry.in_memory[w] != 0: the state never went
+ * through Load): every OUT row is an upsert, nothing is deleted, condition = 0 — the write
+ * is a snapshot / conflict-resolve write */
+#define CDR_MUT_SNAPSHOT 0x1u
+typedef struct cdr_mut_info { /* per entry */
+  int32_t code;               /* CDR_MUT_*: NOT_OK = the entry's replay result is not CDR_OK (or its
+                               * carry.src is past carry.n_src); E_ORDER = one of its tables is not
+                               * in ascending unique key order.  Both: all counts 0 */
+  uint32_t flags;             /* CDR_MUT_SNAPSHOT */
+  int64_t condition;          /* nextEventIDInDB (0 for snapshot entries) */
+  uint32_t n_del_act, n_del_timer, n_del_child, n_del_cancel, n_del_signal, _pad;
+} cdr_mut_info;
+#ifdef __cplusplus
+static_assert(sizeof(cdr_mut_info) == 40, "cdr_mut_info");
+#endif
+typedef struct cdr_mutation {
+  /* cdr_out-shaped view with the capacities of the replay's `out` (in->caps).  The call writes
+   * upsert.result[w] — out->result[w] with n_activity .. n_signal replaced by the upsert counts
+   * (entries that are not CDR_OK: copied as they are) — and the five pending tables: entry w's
+   * upserts at the front of its own slice in ascending key order, rows past the count
+   * untouched.  exec / repl / vh / rp / sa are the caller's to point at the replay's own
+   * buffers (they are always written whole); transfer, n_tasks and last_decision are ignored.
+   * upsert.result and the tables must not alias `out`'s. */
+  cdr_out upsert;
+  /* delete keys, ascending: entry w's at carry.caps[carry.src[w]].*_off of arrays sized by
+   * carry.totals (an entry deletes at most the rows it loaded), counts in info */
+  int64_t* del_act;    /* [carry.totals.act]    schedule_id */
+  int64_t* del_timer;  /* [carry.totals.timer]  timer_id handle, zero-extended */
+  int64_t* del_child;  /* [carry.totals.child]  initiated_id */
+  int64_t* del_cancel; /* [carry.totals.cancel] */
+  int64_t* del_signal; /* [carry.totals.signal] */
+  cdr_mut_info* info;  /* [n_wfs] */
+} cdr_mutation;
+
 /* ==================================================== NDC VERSION HISTORIES ===
  * The persisted VersionHistories of an NDC workflow (common/persistence/versionHistory.go:
  * VersionHistories{currentVersionHistoryIndex, histories []*VersionHistory}), one branch
