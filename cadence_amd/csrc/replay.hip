@@ -815,7 +815,9 @@ __global__ __launch_bounds__(CDR_SLICE_WIDTH) __attribute__((amdgpu_waves_per_eu
   }
 
   // ---- transfer / timer tasks (stateBuilder.go:613-804), when the caller asks for
-  // them (cdr_out.transfer != NULL): appended in generation order to the entry's slices
+  // them (cdr_out.transfer != NULL): appended in generation order to the entry's slices.
+  // n_xt / n_tt count every record, stored or not: a count past its capacity fails the entry
+  // after the loop (schema.h CDR_E_BAD_INPUT)
   constexpr bool TK = TASKS;  // instantiated without task code for the common case
   uint32_t n_xt = 0, n_tt = 0, xt_cap = 0, tt_cap = 0;
   if (TK) {
@@ -824,8 +826,7 @@ __global__ __launch_bounds__(CDR_SLICE_WIDTH) __attribute__((amdgpu_waves_per_eu
   }
   auto task_x = [&](bool c, uint32_t type, int64_t eid, uint32_t dom, uint32_t tl, uint32_t twf, uint32_t trun,
                     uint32_t fl) {
-    c = c && n_xt < xt_cap;
-    if (c) {
+    if (c && n_xt < xt_cap) {
       cdr_task t;
       t.type = type;
       t.timeout_type = 0;
@@ -844,8 +845,7 @@ __global__ __launch_bounds__(CDR_SLICE_WIDTH) __attribute__((amdgpu_waves_per_eu
     n_xt += c ? 1u : 0u;
   };
   auto task_t = [&](bool c, uint32_t type, int32_t tt, int64_t eid, int64_t vis, int64_t att) {
-    c = c && n_tt < tt_cap;
-    if (c) {
+    if (c && n_tt < tt_cap) {
       cdr_task t;
       t.type = type;
       t.timeout_type = tt;
@@ -1036,6 +1036,7 @@ __global__ __launch_bounds__(CDR_SLICE_WIDTH) __attribute__((amdgpu_waves_per_eu
           const bool ok = mine && !f1 && !f2;
           const bool first = !(x_flags & CDR_XI_STARTED);  // fields absent from a first Started stay zero
           uint32_t nrp = n_rp, nsa = n_sa, xf = x_flags;
+          bool f_cap = false;  // the event's reset points or search attributes do not fit their slices
           if (ok) {  // output-record side effects (lane-masked)
             X->domain_id = D.domain_id;
             X->workflow_id = D.workflow_id;
@@ -1086,6 +1087,7 @@ __global__ __launch_bounds__(CDR_SLICE_WIDTH) __attribute__((amdgpu_waves_per_eu
               const int64_t expiring = e.ts + (int64_t)D.retention_days * 24ll * 3600ll * NS_PER_S;
               const uint32_t crun = a->continued_run_id, off = a->reset_points_off, cnt = a->reset_points_len;
               const uint32_t cap = CP.rp_cap;
+              f_cap |= cnt > cap;
               for (uint32_t q = 0; q < cnt && q < cap; q++) {
                 cdr_reset_point p = gget(gp(B_.rps) + (off + q));
                 const uint32_t run = (p.flags & CDR_RP_HAS_RUN_ID) ? p.run_id : 0u;
@@ -1105,6 +1107,7 @@ __global__ __launch_bounds__(CDR_SLICE_WIDTH) __attribute__((amdgpu_waves_per_eu
             if (af & CDR_SF_HAS_SEARCH_ATTR) {
               nsa = 0;
               const uint32_t off = a->search_attr_off, cnt = a->search_attr_len, cap = CP.sa_cap;
+              f_cap |= cnt > cap;
               for (uint32_t q = 0; q < cnt && q < cap; q++) gput(sa + nsa++, gget(gp(B_.kvs) + (off + q)));
               if (nsa) xf |= CDR_XI_HAS_SEARCH_ATTR;
               else xf &= ~CDR_XI_HAS_SEARCH_ATTR;
@@ -1118,6 +1121,7 @@ __global__ __launch_bounds__(CDR_SLICE_WIDTH) __attribute__((amdgpu_waves_per_eu
             X->branch_id_hi = hi;
             if (isRS) RS->start_version = e.ver;  // :182-184
           }
+          PFAIL(f_cap, CDR_E_BAD_INPUT);
           n_rp = SEL(ok, nrp, n_rp);
           n_sa = SEL(ok, nsa, n_sa);
           x_flags = SEL(ok, xf, x_flags);
@@ -1534,6 +1538,7 @@ __global__ __launch_bounds__(CDR_SLICE_WIDTH) __attribute__((amdgpu_waves_per_eu
         }
         case CDR_EV_UPSERT_SA: {  // :533-535 -> :2746-2768
           uint32_t nsa = n_sa;
+          bool f_cap = false;  // a new key past the search-attribute slice
           if (mine) {
             const uint64_t off = (uint64_t)e.aux;
             const uint32_t cnt = e.h, cap = CP.sa_cap;
@@ -1546,8 +1551,10 @@ __global__ __launch_bounds__(CDR_SLICE_WIDTH) __attribute__((amdgpu_waves_per_eu
                   found = true;
                 }
               if (!found && nsa < cap) gput(sa + nsa++, kv);
+              else f_cap |= !found;
             }
           }
+          PFAIL(f_cap, CDR_E_BAD_INPUT);
           n_sa = SEL(mine, nsa, n_sa);
           x_flags |= mine ? CDR_XI_HAS_SEARCH_ATTR : 0u;
           task_x(TK && mine, CDR_TT_UPSERT_SA, 0, 0, 0, 0, 0, 0);  // :535
@@ -1601,6 +1608,11 @@ __global__ __launch_bounds__(CDR_SLICE_WIDTH) __attribute__((amdgpu_waves_per_eu
   }
   if (err == CDR_OK && D.parent < 0 && D.expected_next_event_id != 0 && x_next_event != D.expected_next_event_id) {
     err = CDR_E_REBUILD_NEXT_EVENT_ID;  // nDCStateRebuilder.go:139-143
+    err_id = prev_id;
+    err_k = len;
+  }
+  if (TK && err == CDR_OK && (n_xt > xt_cap || n_tt > tt_cap)) {  // a task list past its slice
+    err = CDR_E_BAD_INPUT;
     err_id = prev_id;
     err_k = len;
   }
@@ -1946,7 +1958,16 @@ __global__ __launch_bounds__(CDR_SLICE_WIDTH) CDR_MERGE_ATTR void k_tasks_merge(
   if (valid) {  // (a truncated list is not returned: the entry reports the bad capacities)
     KA()->O.n_tasks[2ull * (uint64_t)w] = lost ? 0u : n_xt;
     KA()->O.n_tasks[2ull * (uint64_t)w + 1] = lost ? 0u : n_tt;
-    if (lost) KA()->O.result[w].code = CDR_E_BAD_INPUT;
+    if (lost) {  // as k_replay_reg's t_over: failed at the end of the history, no state emitted
+      cdr_wf_result r = KA()->O.result[w];
+      r.code = CDR_E_BAD_INPUT;
+      r.flags &= ~RF_ROWS_SORTED;
+      r.fail_event_id = KA()->O.exec[w].next_event_id - 1;  // the last event's id (the entry replayed whole)
+      r.fail_index = (int64_t)KA()->B.wfs[w].ev_len;
+      r.n_activity = r.n_timer = r.n_child = r.n_cancel = r.n_signal = r.n_vh = 0;
+      r.n_reset_points = r.n_search_attr = 0;
+      KA()->O.result[w] = r;
+    }
   }
 }
 

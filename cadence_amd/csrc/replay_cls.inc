@@ -1219,6 +1219,7 @@ __global__ __launch_bounds__(PAR ? 4 * CDR_SLICE_WIDTH : CDR_SLICE_WIDTH)
                 const int64_t expiring = ts0 + (int64_t)Dh->retention_days * 24ll * 3600ll * NS_PER_S;
                 const uint32_t crun = a->continued_run_id, off = a->reset_points_off, cnt = a->reset_points_len;
                 const uint32_t cap = CPh->rp_cap;
+                rty |= cnt > cap;  // the points do not fit the slice: k_replay_reg reports it
                 for (uint32_t qq = 0; qq < cnt && qq < cap && u_nrp < LY::NRP; qq++) {
                   cdr_reset_point pr = gget(gp(B_.rps) + (off + qq));
                   const uint32_t run = (pr.flags & CDR_RP_HAS_RUN_ID) ? pr.run_id : 0u;
@@ -1239,6 +1240,7 @@ __global__ __launch_bounds__(PAR ? 4 * CDR_SLICE_WIDTH : CDR_SLICE_WIDTH)
               if (af & CDR_SF_HAS_SEARCH_ATTR) {
                 u_nsa = 0;
                 const uint32_t off = a->search_attr_off, cnt = a->search_attr_len, cap = CPh->sa_cap;
+                rty |= cnt > cap;
                 for (uint32_t qq = 0; qq < cnt && qq < cap && u_nsa < CDR_REG_NSA; qq++) {
                   const cdr_kv kv = gget(gp(B_.kvs) + (off + qq));
                   if (lane == 0) gput(sah + u_nsa, kv);
@@ -1368,7 +1370,7 @@ __global__ __launch_bounds__(PAR ? 4 * CDR_SLICE_WIDTH : CDR_SLICE_WIDTH)
             while (cand) {
               const uint32_t j = (uint32_t)__builtin_ctzll(cand);
               const uint32_t c = rdl(cks, j);
-              if (u_nrp >= LY::NRP) {  // the planner's bound (CDR_CAP_REG): never taken
+              if (u_nrp >= LY::NRP || u_nrp >= CPh->rp_cap) {  // the planner's bound (CDR_CAP_REG), or the slice
                 rty = true; why |= 32u;
                 break;
               }
@@ -1442,6 +1444,8 @@ __global__ __launch_bounds__(PAR ? 4 * CDR_SLICE_WIDTH : CDR_SLICE_WIDTH)
                     sa_k = lane == u_nsa ? kk : sa_k;
                     sa_v = lane == u_nsa ? kv_ : sa_v;
                     u_nsa++;
+                  } else {
+                    rty |= u_nsa >= cap;  // a new key past the slice: k_replay_reg reports it
                   }
                 }
               }
@@ -1460,6 +1464,8 @@ __global__ __launch_bounds__(PAR ? 4 * CDR_SLICE_WIDTH : CDR_SLICE_WIDTH)
               if (!found && u_nsa < cap && u_nsa < CDR_REG_NSA) {
                 if (lane == 0) gput(sah + u_nsa, kv);
                 u_nsa++;
+              } else {
+                rty |= !found && u_nsa >= cap;
               }
               vmdrain();
             }
@@ -1618,6 +1624,7 @@ __global__ __launch_bounds__(PAR ? 4 * CDR_SLICE_WIDTH : CDR_SLICE_WIDTH)
           const int64_t expiring = e.ts + (int64_t)D.retention_days * 24ll * 3600ll * NS_PER_S;
           const uint32_t crun = a->continued_run_id, off = a->reset_points_off, cnt = a->reset_points_len;
           const uint32_t cap = CP.rp_cap;
+          retry |= cnt > cap;  // the points do not fit the slice: k_replay_reg reports it
           for (uint32_t q = 0; q < cnt && q < cap && n_rp < LY::NRP; q++) {
             cdr_reset_point pr = gget(gp(B_.rps) + (off + q));
             const uint32_t run = (pr.flags & CDR_RP_HAS_RUN_ID) ? pr.run_id : 0u;
@@ -1636,6 +1643,7 @@ __global__ __launch_bounds__(PAR ? 4 * CDR_SLICE_WIDTH : CDR_SLICE_WIDTH)
         if (af & CDR_SF_HAS_SEARCH_ATTR) {
           n_sa = 0;
           const uint32_t off = a->search_attr_off, cnt = a->search_attr_len, cap = CP.sa_cap;
+          retry |= cnt > cap;
           for (uint32_t q = 0; q < cnt && q < cap && n_sa < CDR_REG_NSA; q++) {
             gput(sa + n_sa, gget(gp(B_.kvs) + (off + q)));
             n_sa++;
@@ -1779,7 +1787,8 @@ __global__ __launch_bounds__(PAR ? 4 * CDR_SLICE_WIDTH : CDR_SLICE_WIDTH)
 #pragma unroll
         for (uint32_t q = 0; q < LY::NRP; q++) exists |= chk && q < n_rp && rl(RP0 + 2 * q, lane) == cks;
         const bool app = chk && !exists;
-        const bool f = app && n_rp >= LY::NRP;  // the planner's bound (CDR_CAP_REG): never taken
+        // the planner's bound (CDR_CAP_REG): never taken; the entry's slice: k_replay_reg reports it
+        const bool f = app && (n_rp >= LY::NRP || n_rp >= CP.rp_cap);
         retry |= f;
         const bool put = app && !f;
         if (put) {  // Resettable is settled in the X loop; the row is written after it
@@ -1859,6 +1868,8 @@ __global__ __launch_bounds__(PAR ? 4 * CDR_SLICE_WIDTH : CDR_SLICE_WIDTH)
           if (!found && n_sa < cap && n_sa < CDR_REG_NSA) {
             gput(sa + n_sa, kv);
             n_sa++;
+          } else {
+            retry |= !found && n_sa >= cap;  // a new key past the slice: k_replay_reg reports it
           }
           vmdrain();
         }

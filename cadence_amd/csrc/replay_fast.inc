@@ -205,10 +205,12 @@ k_replay_fast(cdr_launch L) {
   };
   auto task_x = [&](bool c, uint32_t type, int64_t eid, uint32_t dom, uint32_t tl) __attribute__((always_inline)) {
     if constexpr (TASKS) {
-      c = c && n_xt < t_xcap;
+      // n_xt counts every record, stored or not: a count past the capacity fails the entry
+      // after the loop (schema.h CDR_E_BAD_INPUT)
+      const bool st = c && n_xt < t_xcap;
       if constexpr (CDR_FAST_TBUF > 0) {
-        tq_put(c, 0u, type, 0, t_xoff + n_xt, eid, (int64_t)(dom | ((uint64_t)tl << 32)));
-      } else if (c) {
+        tq_put(st, 0u, type, 0, t_xoff + n_xt, eid, (int64_t)(dom | ((uint64_t)tl << 32)));
+      } else if (st) {
         cdr_task t;
         t.type = type;
         t.timeout_type = 0;
@@ -226,10 +228,10 @@ k_replay_fast(cdr_launch L) {
   };
   auto task_t = [&](bool c, uint32_t type, int32_t tt, int64_t eid, int64_t vis) __attribute__((always_inline)) {
     if constexpr (TASKS) {
-      c = c && n_tt < t_tcap;
+      const bool st = c && n_tt < t_tcap;
       if constexpr (CDR_FAST_TBUF > 0) {
-        tq_put(c, 1u, type, tt, t_toff + n_tt, eid, vis);
-      } else if (c) {
+        tq_put(st, 1u, type, tt, t_toff + n_tt, eid, vis);
+      } else if (st) {
         cdr_task t;
         t.type = type;
         t.timeout_type = tt;
@@ -418,12 +420,14 @@ k_replay_fast(cdr_launch L) {
         __builtin_amdgcn_s_waitcnt(0xC07F);
         __builtin_amdgcn_wave_barrier();
       }
+      bool f_cap = false;  // the event's reset points or search attributes do not fit their slices
       if (ok) {
         if (af & CDR_SF_HAS_RESET_POINTS) {  // rolloverAutoResetPointsWithExpiringTime (:3184-3205)
           xf |= CDR_XI_HAS_RESET_POINTS;
           const int64_t expiring = e.ts + (int64_t)D.retention_days * 24ll * 3600ll * NS_PER_S;
           const uint32_t crun = a->continued_run_id, off = a->reset_points_off, cnt = a->reset_points_len;
           const uint32_t cap = CP.rp_cap;
+          f_cap |= cnt > cap;
           for (uint32_t q = 0; q < cnt && q < cap; q++) {
             cdr_reset_point p = gget(gp(B_.rps) + (off + q));
             const uint32_t run = (p.flags & CDR_RP_HAS_RUN_ID) ? p.run_id : 0u;
@@ -438,10 +442,12 @@ k_replay_fast(cdr_launch L) {
         xf |= (af & CDR_SF_HAS_MEMO) ? CDR_XI_HAS_MEMO : 0u;
         if (af & CDR_SF_HAS_SEARCH_ATTR) {
           const uint32_t off = a->search_attr_off, cnt = a->search_attr_len, cap = CP.sa_cap;
+          f_cap |= cnt > cap;
           for (uint32_t q = 0; q < cnt && q < cap; q++) gput(sa + nsa++, gget(gp(B_.kvs) + (off + q)));
           xf |= nsa ? CDR_XI_HAS_SEARCH_ATTR : 0u;
         }
       }
+      PFAIL(f_cap, CDR_E_BAD_INPUT);
       n_rp = SEL(ok, nrp, n_rp);
       n_sa = SEL(ok, nsa, n_sa);
       x_flags = SEL(ok, xf, x_flags);
@@ -821,6 +827,11 @@ k_replay_fast(cdr_launch L) {
   if (len > 0 && err == CDR_OK) x_next_event = prev_id + 1;
   if (err == CDR_OK && D.parent < 0 && D.expected_next_event_id != 0 && x_next_event != D.expected_next_event_id) {
     err = CDR_E_REBUILD_NEXT_EVENT_ID;  // nDCStateRebuilder.go:139-143
+    err_id = prev_id;
+    err_k = len;
+  }
+  if (TASKS && err == CDR_OK && (n_xt > t_xcap || n_tt > t_tcap)) {  // a task list past its slice
+    err = CDR_E_BAD_INPUT;
     err_id = prev_id;
     err_k = len;
   }

@@ -574,7 +574,8 @@ __device__ __forceinline__ void reg_slice(const uint32_t s) {
 #pragma unroll
         for (uint32_t q = 0; q < LY::NRP; q++) exists |= chk && q < n_rp && rl(RP0 + 2 * q, lane) == cks;
         const bool app = chk && !exists;
-        const bool f = app && n_rp >= LY::NRP;  // the planner's bound (CDR_CAP_REG): never taken
+        // the planner's bound (CDR_CAP_REG): never taken; the entry's slice: too small a capacity
+        const bool f = app && (n_rp >= LY::NRP || n_rp >= CP.rp_cap);
         CAPFAIL(f);
         const bool put = app && !f;
         if (put) {  // the row is written after the loop (its first decision-completed id is event k's)
@@ -955,6 +956,7 @@ __device__ __forceinline__ void reg_slice(const uint32_t s) {
             const int64_t expiring = e.ts + (int64_t)D.retention_days * 24ll * 3600ll * NS_PER_S;
             const uint32_t crun = a->continued_run_id, off = a->reset_points_off, cnt = a->reset_points_len;
             const uint32_t cap = CP.rp_cap;
+            PFAIL(cnt > cap, CDR_E_BAD_INPUT);  // the rolled-over points do not fit the slice
             if constexpr (CARRY) cyr |= (cnt < cap ? cnt : cap) > LY::NRP;
             for (uint32_t q = 0; q < cnt && q < cap && n_rp < LY::NRP; q++) {
               cdr_reset_point p = gget(gp(B_.rps) + (off + q));
@@ -978,6 +980,7 @@ __device__ __forceinline__ void reg_slice(const uint32_t s) {
           if (af & CDR_SF_HAS_SEARCH_ATTR) {
             n_sa = 0;
             const uint32_t off = a->search_attr_off, cnt = a->search_attr_len, cap = CP.sa_cap;
+            PFAIL(cnt > cap, CDR_E_BAD_INPUT);  // the search attributes do not fit the slice
             if constexpr (CARRY) cyr |= (cnt < cap ? cnt : cap) > CDR_REG_NSA;
             for (uint32_t q = 0; q < cnt && q < cap && n_sa < CDR_REG_NSA; q++) {
               gput(sa + n_sa, gget(gp(B_.kvs) + (off + q)));
@@ -1028,6 +1031,8 @@ __device__ __forceinline__ void reg_slice(const uint32_t s) {
             n_sa++;
           } else if (CARRY && !found && n_sa < cap) {
             cyr = true;  // a key beyond this variant's search-attribute rows
+          } else {
+            PFAIL(!found && n_sa >= cap, CDR_E_BAD_INPUT);  // a new key past the slice
           }
           vmdrain();
         }

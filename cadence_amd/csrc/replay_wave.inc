@@ -406,6 +406,7 @@ __global__ __launch_bounds__(CDR_SLICE_WIDTH) __attribute__((amdgpu_waves_per_eu
           const uint32_t crun = u32(a->continued_run_id), off = u32(a->reset_points_off);
           const uint32_t cnt = u32(a->reset_points_len), cap = u32(CP.rp_cap);
           const uint32_t m = cnt < cap ? cnt : cap;
+          if (cnt > cap) FAILW(CDR_E_BAD_INPUT);  // the rolled-over points do not fit the slice
           for (uint32_t q0 = 0; q0 < m; q0 += 64) {
             const uint32_t q = q0 + lane;
             if (q < m) {
@@ -424,6 +425,7 @@ __global__ __launch_bounds__(CDR_SLICE_WIDTH) __attribute__((amdgpu_waves_per_eu
         if (af & CDR_SF_HAS_SEARCH_ATTR) {
           const uint32_t off = u32(a->search_attr_off), cnt = u32(a->search_attr_len), cap = u32(CP.sa_cap);
           const uint32_t m = cnt < cap ? cnt : cap;
+          if (cnt > cap) FAILW(CDR_E_BAD_INPUT);  // the search attributes do not fit the slice
           for (uint32_t q0 = 0; q0 < m; q0 += 64) {  // pairs past the lanes live in the rows only
             const uint32_t q = q0 + lane;
             if (q < m) {
@@ -841,6 +843,8 @@ __global__ __launch_bounds__(CDR_SLICE_WIDTH) __attribute__((amdgpu_waves_per_eu
             if (L0) gput(sa + n_sa, cdr_kv{kk, vv});
             if (lane == n_sa) sa_key = kk;
             n_sa++;
+          } else if (!found) {
+            FAILW(CDR_E_BAD_INPUT);  // a new key past the slice
           }
         }
         x_flags |= CDR_XI_HAS_SEARCH_ATTR;

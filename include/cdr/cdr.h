@@ -482,7 +482,16 @@ int cdr_set_plan_mode(cdr_ctx* ctx, uint32_t mode);
  * (replay_cls.inc, k_tasks_merge); the workspace is sized from the batch's task-slice total,
  * which the first launch over a batch (a new in->caps pointer or entry count) reads back with
  * one blocking 40-byte copy of in->caps[n_wfs - 1] — later launches over the same batch stay
- * fully asynchronous.  A plan with task lists must have no wave slices (CDR_API_EINVAL). */
+ * fully asynchronous.  A plan with task lists must have no wave slices (CDR_API_EINVAL).
+ * Capacities (in->caps): every kernel writes an entry's rows into [*_off, *_off + *_cap) of
+ * the caller's tables and nowhere else.  An entry whose grow-only state slices (vh_cap,
+ * rp_cap, sa_cap) or task slices (xfer_cap, ttask_cap) cannot hold what its history produces
+ * ends with CDR_E_BAD_INPUT, all n_* counts and both n_tasks zero, on every kernel route, and
+ * leaves every other entry of the batch unaffected (schema.h CDR_E_BAD_INPUT: the failure
+ * location).  The five pending-table capacities (act_cap .. signal_cap) are outside this
+ * contract: they must be the planner's values (cdr_plan_caps / cdr_plan_ndc_apply) — the lane
+ * kernels size their working sets from act_live / timer_live and the CDR_CAP_* flags and never
+ * read them, the wave kernel uses them as working bounds. */
 int cdr_replay_sliced_async(cdr_ctx* ctx, const cdr_dev_batch* in, const cdr_out* out, void* stream);
 
 /* Whole pipeline for host-resident data: plan + pack + H2D + replay + D2H on `stream`

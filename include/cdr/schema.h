@@ -155,7 +155,16 @@ enum cdr_status {
   CDR_E_MISSING_ACTIVITY_INFO = 10, /* ReplicateActivityTaskCancelRequested :2270-2273 */
   CDR_E_DOMAIN_NOT_FOUND = 11,      /* domain cache lookups stateBuilder.go:162,365,417,448 */
   CDR_E_REBUILD_NEXT_EVENT_ID = 12, /* nDCStateRebuilder.go:139-143 */
-  CDR_E_BAD_INPUT = 13,             /* malformed batch (host validation) */
+  /* malformed batch (host validation), or an entry whose grow-only state slices (vh_cap, rp_cap,
+   * sa_cap) or task slices (xfer_cap, ttask_cap) cannot hold what its history produces.  Such an
+   * entry has all n_* counts and both n_tasks zero, no byte written outside [off, off + cap) of
+   * any of its tables, and leaves the batch's other entries unaffected.  Location: a task slice —
+   * (fail_event_id, fail_index) = (the entry's last event id, ev_len), the lists being complete
+   * only at the end of the history; a state slice — the first event whose row did not fit, its
+   * id and index as for any other mid-history failure (the CPU restatement checks at the end
+   * and reports no location for these).  The pending-table capacities (act_cap .. signal_cap)
+   * are not covered: they must be the planner's values. */
+  CDR_E_BAD_INPUT = 13,
   /* refreshTasks (cdr_refresh_tasks_async; mutableStateTaskRefresher.go:66-160) */
   CDR_E_REFRESH_EVENT_NOT_FOUND = 14, /* GetStartEvent / eventsCache.getEvent miss: the event is not
                                          among the entry's own events (e.g. a carried-in entry) */

@@ -978,7 +978,6 @@ static void sorted_values(const std::map<K, T>& m, std::vector<T>& out) {
 }
 
 bool write_state(const MutableState& ms, const cdr_batch* b, uint32_t w, const cdr_wf_caps* caps, cdr_out* out) {
-  (void)b;
   if (out->last_decision) out->last_decision[w] = ms.lastDecision;
   const ExecutionInfo& ei = ms.ei;
   const cdr_wf_caps& cp = caps[w];
@@ -1071,6 +1070,13 @@ bool write_state(const MutableState& ms, const cdr_batch* b, uint32_t w, const c
       ms.pendingRequestCancelInfoIDs.size() > cp.cancel_cap || ms.pendingSignalInfoIDs.size() > cp.signal_cap ||
       ei.ResetPoints.size() > cp.rp_cap || sa.size() > cp.sa_cap)
     return false;
+  // a task list past its slice fails the entry at the end of its history (schema.h
+  // CDR_E_BAD_INPUT): no state, no tasks
+  if (out->transfer && (ms.transferTasks.size() > cp.xfer_cap || ms.timerTasks.size() > cp.ttask_cap)) {
+    r.fail_event_id = b->wfs[w].ev_len ? b->events[b->wfs[w].ev_off + b->wfs[w].ev_len - 1].event_id : 0;
+    r.fail_index = (int64_t)b->wfs[w].ev_len;
+    return false;
+  }
 
   r.n_vh = (uint32_t)ms.vh.items.size();
   for (size_t k = 0; k < ms.vh.items.size(); k++)
@@ -1158,7 +1164,6 @@ bool write_state(const MutableState& ms, const cdr_batch* b, uint32_t w, const c
   for (size_t j = 0; j < sa.size(); j++) out->sa[cp.sa_off + j] = sa[j];
   r.n_search_attr = (uint32_t)sa.size();
   if (out->transfer) {
-    if (ms.transferTasks.size() > cp.xfer_cap || ms.timerTasks.size() > cp.ttask_cap) return false;
     for (size_t j = 0; j < ms.transferTasks.size(); j++) out->transfer[cp.xfer_off + j] = ms.transferTasks[j];
     for (size_t j = 0; j < ms.timerTasks.size(); j++) out->timer_tasks[cp.ttask_off + j] = ms.timerTasks[j];
     out->n_tasks[2 * w] = (uint32_t)ms.transferTasks.size();
@@ -1325,6 +1330,7 @@ void replay_one(const cdr_batch* b, const Ctx* ctx, uint32_t w, const cdr_wf_cap
   const cdr_wf_desc& d = b->wfs[w];
   cdr_wf_result& r = out->result[w];
   r = cdr_wf_result{};
+  if (out->n_tasks) out->n_tasks[2 * w] = out->n_tasks[2 * w + 1] = 0;  // a failed entry reports no tasks
   MutableState ms(ctx, (int)d.builder, d.failover_version, d.wf_key, d.retention_days);
   if (b->carry && b->carry->src && b->carry->src[w] >= 0) {
     load_state(ms, *b->carry, (uint32_t)b->carry->src[w]);
