@@ -54,7 +54,7 @@ STATUS = {
     16: "E_REFRESH_CAPACITY", 17: "E_VH_NO_LCA", 18: "E_VH_LCA_NOT_CONTAINED", 19: "E_VH_FIRST_ITEM_MISMATCH",
     20: "E_NDC_RETRY_TASK", 21: "E_NDC_BRANCH_CHANGED", 22: "E_NDC_SAME_VERSION", 23: "E_REBUILD_VH_MISMATCH",
     24: "E_VHS_CAPACITY", 25: "E_VH_EMPTY", 32: "P_ACTIVITY_STARTED_NIL", 33: "P_CHILD_STARTED_NIL",
-    34: "P_VH_ITEM_INVALID", 35: "P_UNKNOWN_CLUSTER", 64: "NOT_APPLIED", 65: "NOT_RUN",
+    34: "P_VH_ITEM_INVALID", 35: "P_UNKNOWN_CLUSTER", 36: "P_UNKNOWN_WF_STATE", 64: "NOT_APPLIED", 65: "NOT_RUN",
 }
 OK = 0
 E_HISTORY_EMPTY = 1
@@ -236,6 +236,27 @@ CdrMutInfo = _S("cdr_mut_info", [("code", i32), ("flags", u32), ("condition", i6
                                  ("n_del_signal", u32), ("_pad", u32)])
 CdrMutation = _S("cdr_mutation", [("upsert", CdrOut)] + [(n, C.c_void_p) for n in (
     "del_act", "del_timer", "del_child", "del_cancel", "del_signal", "info")])
+# SyncActivity on loaded states (schema.h cdr_sync_activity / cdr_sync_result)
+CdrSyncActivity = _S("cdr_sync_activity", [
+    ("version", i64), ("scheduled_id", i64), ("scheduled_time", i64), ("started_id", i64), ("started_time", i64),
+    ("last_heartbeat_time", i64), ("attempt", i32), ("wf", i32), ("tag", u64)])
+CdrSyncResult = _S("cdr_sync_result", [
+    ("action", i32), ("code", i32), ("flags", u32), ("_pad", u32), ("next_event_id", i64), ("event_time", i64),
+    ("last_write_version", i64), ("act_row", u32), ("task_row", u32), ("tag", u64), ("_pad1", u64),
+    ("timer_task", CdrTask)])
+(SYNC_SKIP_NO_WORKFLOW, SYNC_SKIP_NOT_RUNNING, SYNC_SKIP_STALE_VERSION, SYNC_RETRY_2DC, SYNC_RETRY_NDC,
+ SYNC_SKIP_NO_ACTIVITY, SYNC_SKIP_LOCAL_VERSION_LARGER, SYNC_SKIP_LOCAL_ATTEMPT_LARGER, SYNC_SKIP_HEARTBEAT_OLDER,
+ SYNC_APPLIED, SYNC_E_STATE) = range(11)
+SYNC_ACTIONS = {0: "SKIP_NO_WORKFLOW", 1: "SKIP_NOT_RUNNING", 2: "SKIP_STALE_VERSION", 3: "RETRY_2DC",
+                4: "RETRY_NDC", 5: "SKIP_NO_ACTIVITY", 6: "SKIP_LOCAL_VERSION_LARGER",
+                7: "SKIP_LOCAL_ATTEMPT_LARGER", 8: "SKIP_HEARTBEAT_OLDER", 9: "APPLIED", 10: "E_STATE"}
+SYNC_RESET_TIMER_STATUS, SYNC_HAS_TIMER_TASK = 0x1, 0x2
+SYNC_NO_ROW = 0xFFFFFFFF
+SYNC_GROUP = 4  # CDR_SYNC_GROUP (cdr.h)
+SYNC_GROUPS = (4, 8, 16, 64)
+AI_HEARTBEAT_TIME_SET = 0x8
+E_VH_EMPTY, P_UNKNOWN_WF_STATE = 25, 36
+TT_ACTIVITY_TIMEOUT = 17
 CdrSlices = _S("cdr_slices", [
     ("n_slices", u32), ("_pad", u32), ("n_rows", u64), ("arena_words", u64)] + [(n, C.c_void_p) for n in (
         "slice_row0", "slice_len", "lane_wf", "slab", "arena", "slice_scratch_off", "slice_act_slots",
@@ -332,6 +353,7 @@ MIRRORS = {
     "cdr_ndc_task": CdrNdcTask, "cdr_ndc_decision": CdrNdcDecision, "cdr_ndc_round": CdrNdcRound, "cdr_last_decision": CdrLastDecision,
     "cdr_opts": CdrOpts, "cdr_ingest_in": CdrIngestIn, "cdr_ingest_out": CdrIngestOut,
     "cdr_mut_info": CdrMutInfo, "cdr_mutation": CdrMutation,
+    "cdr_sync_activity": CdrSyncActivity, "cdr_sync_result": CdrSyncResult,
 }
 
 # C ABI entry points declared in include/cdr/cdr.h and include/cdr/synth.h
@@ -377,6 +399,13 @@ EXPORTS = {
                                  C.c_void_p]),
     "cdr_mutation_batch": (i32, [C.c_void_p, C.POINTER(CdrBatch), C.POINTER(CdrWfCaps), C.POINTER(CdrTotals),
                                  C.POINTER(CdrOut), C.POINTER(CdrMutation), C.c_void_p]),
+    "cdr_plan_sync": (i32, [C.c_void_p, u32, u32, C.c_void_p, C.c_void_p]),
+    "cdr_sync_activity_async": (i32, [C.c_void_p, C.c_void_p, C.c_void_p, u32, u32, C.c_void_p, C.POINTER(CdrOut),
+                                      C.POINTER(CdrClusterMeta), C.c_void_p, C.c_void_p]),
+    "cdr_sync_activity_batch": (i32, [C.c_void_p, C.c_void_p, C.c_void_p, u32, u32, C.c_void_p,
+                                      C.POINTER(CdrTotals), C.POINTER(CdrOut), C.POINTER(CdrClusterMeta), C.c_void_p,
+                                      C.c_void_p]),
+    "cdr_set_sync_group": (i32, [C.c_void_p, i32]),
     "cdr_plan_class_ranges": (i32, [C.c_void_p, u32, C.c_void_p, C.c_void_p]),
     "cdr_compact_async": (i32, [C.c_void_p, i32, C.POINTER(CdrDevBatch), C.POINTER(CdrOut), C.c_void_p,
                                 C.c_void_p, C.c_void_p]),

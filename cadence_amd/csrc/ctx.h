@@ -50,6 +50,8 @@ enum cdr_ws_slot {
   // cdr_mutation_batch (mutation.hip): the mutation's device buffers (the states reuse WS_CY_* / WS_O_*)
   WS_MUT_RESULT, WS_MUT_ACT, WS_MUT_TIMER, WS_MUT_CHILD, WS_MUT_CANCEL, WS_MUT_SIGNAL, WS_MUT_DEL_ACT,
   WS_MUT_DEL_TIMER, WS_MUT_DEL_CHILD, WS_MUT_DEL_CANCEL, WS_MUT_DEL_SIGNAL, WS_MUT_INFO,
+  // cdr_sync_activity_batch (sync.hip): requests, their CSR and results (the states reuse WS_CY_*)
+  WS_SYNC_REQ, WS_SYNC_OFF, WS_SYNC_RES,
   WS_NUM
 };
 
@@ -77,6 +79,7 @@ struct cdr_ctx {
   int reg = 1;                         // cdr_set_reg_path
   int cls = CDR_CLS_ON;                // cdr_set_cls_path (CDR_CLS_*)
   uint32_t plan_mode = CDR_PLAN_WAVE | CDR_PLAN_PAR;  // cdr_set_plan_mode
+  int sync_group = CDR_SYNC_GROUP;     // cdr_set_sync_group
   hipEvent_t ev[4];
   bool timed;
   // optional per-launch timing ring (bench): event pairs around every replay kernel

@@ -1154,6 +1154,23 @@ int32_t cdr_workflow_id_to_shard(const char* workflow_id, size_t len, int32_t nu
   return (int32_t)(cdr_fingerprint32(workflow_id, len) % (uint32_t)num_shards);
 }
 
+// stable counting sort of the requests by state; strangers (wf < 0 or past the states) last
+int cdr_plan_sync(const cdr_sync_activity* reqs, uint32_t n_req, uint32_t n_states, uint32_t* order,
+                  uint32_t* req_off) {
+  if (!req_off || (n_req && (!reqs || !order))) return CDR_API_EINVAL;
+  auto group = [&](uint32_t i) -> uint32_t {
+    const int32_t wf = reqs[i].wf;
+    return wf < 0 || (uint32_t)wf >= n_states ? n_states : (uint32_t)wf;
+  };
+  const uint64_t n_groups = (uint64_t)n_states + 1;
+  std::fill(req_off, req_off + n_groups + 1, 0u);
+  for (uint32_t i = 0; i < n_req; i++) req_off[group(i) + 1]++;
+  for (uint64_t s = 0; s < n_groups; s++) req_off[s + 1] += req_off[s];
+  std::vector<uint32_t> pos(req_off, req_off + n_groups);
+  for (uint32_t i = 0; i < n_req; i++) order[pos[group(i)]++] = i;
+  return CDR_API_OK;
+}
+
 const char* cdr_version(void) { return "cadence_amd-cdr 0.1 (gfx950)"; }
 
 }  // extern "C"
@@ -1204,6 +1221,8 @@ uint64_t cdr_struct_size(const char* name) {
       {"cdr_ndc_round", sizeof(cdr_ndc_round)},
       {"cdr_mut_info", sizeof(cdr_mut_info)},
       {"cdr_mutation", sizeof(cdr_mutation)},
+      {"cdr_sync_activity", sizeof(cdr_sync_activity)},
+      {"cdr_sync_result", sizeof(cdr_sync_result)},
   };
   for (const E& e : table)
     if (std::strcmp(e.n, name) == 0) return e.s;

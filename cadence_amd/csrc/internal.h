@@ -7,6 +7,49 @@
 
 namespace cdr_internal {
 
+// loadActivityTimers (timerBuilder.go:249-312) for one pending row with a schedule ID: the
+// first of the row's timers by (time, order) — between rows the tie key is the schedule ID,
+// so the head of the sorted list is the smallest (t, schedule_id, order) over the rows.
+// Order: ScheduleToClose 0 < StartToClose / ScheduleToStart 1 < Heartbeat 2.  Shared by
+// refreshTasks (refresh.hip) and SyncActivity (sync.hip).
+struct act_timer {
+  int64_t t;
+  int32_t order, type;  // type: cdr_timeout_type
+};
+// (Row: cdr_activity_info, or any record with its scheduled_time, expiration_time, started_id,
+// started_time, last_heartbeat_time, s2s, s2c, stc, hb and flags)
+template <class Row>
+CDR_HD act_timer act_first_timer(const Row& a) {
+  constexpr int64_t kSec = 1000000000LL;
+  act_timer best;
+  int64_t s2c = a.scheduled_time + (int64_t)a.s2c * kSec;
+  if (a.expiration_time < s2c) s2c = a.expiration_time;
+  best.t = s2c, best.order = 0, best.type = CDR_TIMEOUT_SCHEDULE_TO_CLOSE;
+  auto cand = [&](int64_t t, int order, int type) {
+    if (t < best.t) best.t = t, best.order = order, best.type = type;
+  };
+  if (a.started_id != CDR_EMPTY_EVENT_ID) {
+    const bool set = (a.flags & CDR_AI_STARTED_TIME_SET) != 0;
+    const int64_t st = set ? a.started_time : 0;
+    cand(st + (int64_t)a.stc * kSec, 1, CDR_TIMEOUT_START_TO_CLOSE);
+    if (a.hb > 0) {
+      int64_t lhb = set ? a.last_heartbeat_time : 0;
+      if (lhb < st) lhb = st;
+      cand(lhb + (int64_t)a.hb * kSec, 2, CDR_TIMEOUT_HEARTBEAT);
+    }
+  } else {
+    cand(a.scheduled_time + (int64_t)a.s2s * kSec, 1, CDR_TIMEOUT_SCHEDULE_TO_START);
+  }
+  return best;
+}
+// the timer_task_status bit of a timeout type (getActivityTimerStatus, timerBuilder.go:36-47)
+CDR_HD int32_t act_timer_bit(int32_t type) {
+  return type == CDR_TIMEOUT_HEARTBEAT          ? CDR_TTS_HEARTBEAT
+         : type == CDR_TIMEOUT_SCHEDULE_TO_START ? CDR_TTS_SCHEDULE_TO_START
+         : type == CDR_TIMEOUT_SCHEDULE_TO_CLOSE ? CDR_TTS_SCHEDULE_TO_CLOSE
+                                                 : CDR_TTS_START_TO_CLOSE;
+}
+
 // arena words of the attribute record of `type` (0 if the type has none)
 uint32_t arena_words_for(uint32_t type);
 

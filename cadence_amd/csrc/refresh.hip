@@ -20,6 +20,7 @@
 #include <cstdio>
 
 #include "cdr/cdr.h"
+#include "internal.h"
 
 #define HIPCHK(x)                                                                                     \
   do {                                                                                                \
@@ -239,38 +240,19 @@ __global__ __launch_bounds__(256) void k_refresh(cdr_dev_batch B, cdr_out O, int
       }
       if (sched == CDR_EMPTY_EVENT_ID) continue;
       // loadActivityTimers (timerBuilder.go:249-312), first by (time, scheduleID, order)
-      auto cand = [&](int64_t t, int order, int type) {
-        if (best < 0 || t < bt || (t == bt && (sched < bs || (sched == bs && order < bo)))) {
-          best = (int)j;
-          bt = t;
-          bs = sched;
-          bo = order;
-          btype = type;
-        }
-      };
-      int64_t s2c = act[j].scheduled_time + (int64_t)act[j].s2c * kSec;
-      if (act[j].expiration_time < s2c) s2c = act[j].expiration_time;
-      cand(s2c, 0, CDR_TIMEOUT_SCHEDULE_TO_CLOSE);
-      if (started != CDR_EMPTY_EVENT_ID) {
-        const bool set = (act[j].flags & CDR_AI_STARTED_TIME_SET) != 0;
-        const int64_t st = set ? act[j].started_time : 0;
-        cand(st + (int64_t)act[j].stc * kSec, 1, CDR_TIMEOUT_START_TO_CLOSE);
-        if (act[j].hb > 0) {
-          int64_t lhb = set ? act[j].last_heartbeat_time : 0;
-          if (lhb < st) lhb = st;
-          cand(lhb + (int64_t)act[j].hb * kSec, 2, CDR_TIMEOUT_HEARTBEAT);
-        }
-      } else {
-        cand(act[j].scheduled_time + (int64_t)act[j].s2s * kSec, 1, CDR_TIMEOUT_SCHEDULE_TO_START);
+      const cdr_internal::act_timer c = cdr_internal::act_first_timer(act[j]);
+      if (best < 0 || c.t < bt || (c.t == bt && (sched < bs || (sched == bs && c.order < bo)))) {
+        best = (int)j;
+        bt = c.t;
+        bs = sched;
+        bo = c.order;
+        btype = c.type;
       }
     }
     if (code != CDR_OK) break;
     if (best >= 0) {  // GetActivityTimerTaskIfNeeded (timerBuilder.go:211-230), statuses cleared
       T(CDR_TT_ACTIVITY_TIMEOUT, btype, bs, bt, act[best].attempt, 0);
-      best_bit = btype == CDR_TIMEOUT_HEARTBEAT          ? CDR_TTS_HEARTBEAT
-                 : btype == CDR_TIMEOUT_SCHEDULE_TO_START ? CDR_TTS_SCHEDULE_TO_START
-                 : btype == CDR_TIMEOUT_SCHEDULE_TO_CLOSE ? CDR_TTS_SCHEDULE_TO_CLOSE
-                                                           : CDR_TTS_START_TO_CLOSE;
+      best_bit = cdr_internal::act_timer_bit(btype);
     }
     // ---- ForTimer (:319-342): GetUserTimerTaskIfNeeded (timerBuilder.go:171-184)
     const cdr_timer_info* tim = O.timer + cp.timer_off;

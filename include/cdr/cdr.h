@@ -676,6 +676,55 @@ int cdr_mutation_async(cdr_ctx* ctx, const cdr_dev_batch* in, const cdr_out* out
 int cdr_mutation_batch(cdr_ctx* ctx, const cdr_batch* b, const cdr_wf_caps* caps, const cdr_totals* totals,
                        const cdr_out* out, cdr_mutation* mut, void* stream);
 
+/* ---------------------------------------------- SyncActivity (sync.hip) */
+/* Batched historyReplicator.SyncActivity (service/history/historyReplicator.go:160-295) on
+ * loaded states in cdr_out form: per request the walk of its exits (:198-253), then for a
+ * request that applies resetActivityTimerTaskStatus (:261-270; IsVersionFromSameCluster,
+ * common/cluster/metadata.go:163-165), ReplicateActivityInfo on the pending-activity row
+ * (mutableStateBuilder.go:1200-1231) and GetActivityTimerTaskIfNeeded over the state's rows
+ * (timerBuilder.go:211-230,249-312,384-408; ties by time, scheduleID, then ScheduleToClose <
+ * StartToClose / ScheduleToStart < Heartbeat, as refreshTasks).  Requests of one state apply
+ * in order; schema.h cdr_sync_activity / cdr_sync_result describe the records.
+ *
+ * cdr_plan_sync (host): groups n_req requests by state with a stable counting sort by `wf`.
+ * order[i] is the index in `reqs` of the i-th request of the grouped sequence; the requests of
+ * state s are [req_off[s], req_off[s + 1]); requests with wf < 0 or wf >= n_states form a
+ * trailing group [req_off[n_states], req_off[n_states + 1] = n_req), so req_off has
+ * n_states + 2 entries.  The caller gathers reqs through `order` before the calls below. */
+int cdr_plan_sync(const cdr_sync_activity* reqs, uint32_t n_req, uint32_t n_states, uint32_t* order,
+                  uint32_t* req_off);
+/* Applies the grouped requests: reqs [n_req], req_off [at least n_states + 1] (requests from
+ * req_off[n_states] on are the trailing group: SKIP_NO_WORKFLOW for wf < 0, else E_STATE),
+ * state_caps [n_states], the arrays `state` names and res [n_req] are device memory; `state`
+ * and `cluster` themselves are host structs.  Of `state` only result, exec, repl, vh and act
+ * are read; state->act is updated in place (as cdr_ndc_replicate_async updates its `state`):
+ * the synced row's version, scheduled_time, started_id, started_time, last_heartbeat_time,
+ * attempt, flags (CDR_AI_STARTED_TIME_SET iff started, CDR_AI_HEARTBEAT_TIME_SET always) and
+ * timer_task_status, and the bit the timer pick sets on its head row; every other byte of act,
+ * rows of states without an applied request and rows past a state's n_activity keep their
+ * values.  res[i] belongs to reqs[i].  Rows of one state must be in ascending unique
+ * schedule_id order (every replay path writes them so; cdr_mutation_async relies on the same).
+ * One launch, no allocation, no host round trip; asynchronous on `stream`.  CDR_API_EINVAL
+ * for null arguments or cluster->failover_version_increment <= 0. */
+int cdr_sync_activity_async(cdr_ctx* ctx, const cdr_sync_activity* reqs, const uint32_t* req_off, uint32_t n_req,
+                            uint32_t n_states, const cdr_wf_caps* state_caps, const cdr_out* state,
+                            const cdr_cluster_meta* cluster, cdr_sync_result* res, void* stream);
+/* The same for host buffers (as cdr_mutation_batch): the requests, req_off and the states'
+ * result, exec, repl, vh and act records (sized by state_totals) are uploaded into the
+ * context's grow-only workspace, the same kernel runs, then state->act and res are downloaded.
+ * Synchronous on `stream`; one call at a time per context. */
+int cdr_sync_activity_batch(cdr_ctx* ctx, const cdr_sync_activity* reqs, const uint32_t* req_off, uint32_t n_req,
+                            uint32_t n_states, const cdr_wf_caps* state_caps, const cdr_totals* state_totals,
+                            const cdr_out* state, const cdr_cluster_meta* cluster, cdr_sync_result* res,
+                            void* stream);
+/* Lanes that work on one state in the sync kernel: 4, 8, 16 or 64.  The default,
+ * CDR_SYNC_GROUP, is the one tools/sync_bench.py measured fastest on an MI355X (1M config-3
+ * prefix states, one and four requests per workflow: profiles/sync_activity.json).  Returns
+ * the previous value, or CDR_API_EINVAL for another value.  A measurement knob: every value
+ * computes the same bytes. */
+#define CDR_SYNC_GROUP 4
+int cdr_set_sync_group(cdr_ctx* ctx, int lanes);
+
 /* Stream compaction of the per-workflow pending tables into dense tables
  * (device pointers): for each table, rows [caps.off, caps.off + result.n) of every
  * workflow are copied to dense[row_base[w] ...]; row_base is an exclusive scan of

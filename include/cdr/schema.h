@@ -185,6 +185,7 @@ enum cdr_status {
   CDR_P_CHILD_STARTED_NIL = 33,     /* nil deref mutableStateBuilder.go:3319-3320 */
   CDR_P_VH_ITEM_INVALID = 34,       /* NewVersionHistoryItem panic versionHistory.go:36-42 */
   CDR_P_UNKNOWN_CLUSTER = 35,       /* ClusterNameForFailoverVersion panic metadata.go:193-200 */
+  CDR_P_UNKNOWN_WF_STATE = 36,      /* IsWorkflowExecutionRunning panic mutableStateBuilder.go:1432-1433 */
   CDR_NOT_APPLIED = 64,             /* new-run history never applied (parent stopped first) */
   CDR_NOT_RUN = 65                  /* skipped entry of a masked launch (cdr_dev_batch.skip): the
                                        record was not replayed this time (cdr_ndc_replicate_async) */
@@ -412,7 +413,11 @@ typedef struct cdr_batch {
  * records.  Fields that the replay path never writes (StartTimestamp,
  * LastUpdatedTimestamp, ExecutionContext, CompletionEvent, CancelRequestID,
  * Sticky*, Client*, SignalRequestedIDs, BufferedEvents) are omitted: they stay
- * at their zero value on a fresh builder. */
+ * at their zero value on a fresh builder.  The same holds for ActivityInfo's Details,
+ * LastFailureReason, LastWorkerIdentity and LastFailureDetails: the replay never writes
+ * them, and the one path that does — ReplicateActivityInfo (cdr_sync_activity below) —
+ * leaves them with the caller, who copies them from the SyncActivityRequest when the
+ * request's result says CDR_SYNC_APPLIED. */
 
 #define CDR_XI_CANCEL_REQUESTED 0x001u
 #define CDR_XI_HAS_RETRY 0x002u
@@ -471,6 +476,15 @@ typedef struct cdr_vh_item { int64_t event_id, version; } cdr_vh_item;
 #define CDR_AI_CANCEL_REQUESTED 0x1u
 #define CDR_AI_HAS_RETRY 0x2u
 #define CDR_AI_STARTED_TIME_SET 0x4u /* StartedTime / LastHeartBeatUpdatedTime non-zero */
+/* LastHeartBeatUpdatedTime is a real instant although StartedTime may be Go's zero time:
+ * ReplicateActivityInfo (mutableStateBuilder.go:1200-1231) on a request with StartedId ==
+ * EmptyEventID — a retried activity that is scheduled again — clears StartedTime and still
+ * sets the heartbeat time.  Only the sync path (cdr_sync_activity_async) sets and reads this
+ * bit.  The replay kernels, the encoders and the oracle do not know it: a carry-in replay
+ * treats such a row's heartbeat time as zero until ActivityTaskStarted sets both times, which
+ * matches Go in everything the replay reads, because the heartbeat timer exists only for
+ * started activities (timerBuilder.go:269-295). */
+#define CDR_AI_HEARTBEAT_TIME_SET 0x8u
 typedef struct cdr_activity_info { /* ActivityInfo dataInterfaces.go:625-662 */
   int64_t version, schedule_id, scheduled_event_batch_id, scheduled_time;
   int64_t started_id, started_time, last_heartbeat_time, expiration_time;
@@ -747,6 +761,72 @@ typedef struct cdr_mutation {
   int64_t* del_signal; /* [carry.totals.signal] */
   cdr_mut_info* info;  /* [n_wfs] */
 } cdr_mutation;
+
+/* ============================================================ SYNC ACTIVITY ===
+ * historyReplicator.SyncActivity (service/history/historyReplicator.go:160-295) on loaded
+ * states: the replication task the active side sends on every activity heartbeat and every
+ * retried activity start.  One cdr_sync_activity mirrors h.SyncActivityRequest with the fields
+ * the decision and the row need (Details, LastFailureReason, LastWorkerIdentity and
+ * LastFailureDetails stay with the caller, see OUTPUT above). */
+typedef struct cdr_sync_activity {
+  int64_t version, scheduled_id, scheduled_time, started_id, started_time, last_heartbeat_time;
+  int32_t attempt;
+  int32_t wf;   /* index of the loaded state the request addresses (the caller resolves it, as
+                   historyCache does); -1: workflow not found */
+  uint64_t tag; /* the caller's cookie, copied to the result */
+} cdr_sync_activity;
+
+/* one value per exit of SyncActivity, in the reference's order */
+enum cdr_sync_action {
+  CDR_SYNC_SKIP_NO_WORKFLOW = 0,          /* :186-196 EntityNotExists (wf < 0) */
+  CDR_SYNC_SKIP_NOT_RUNNING = 1,          /* :198-201 state Completed / Zombie (mutableStateBuilder.go:1422-1434) */
+  CDR_SYNC_SKIP_STALE_VERSION = 2,        /* :205-214 scheduleID >= nextEventID, version < lastWriteVersion */
+  CDR_SYNC_RETRY_2DC = 3,                 /* :217-227 RetryTaskError, hint = next_event_id */
+  CDR_SYNC_RETRY_NDC = 4,                 /* :228 (also a local builder: its last write version is CDR_EMPTY_VERSION) */
+  CDR_SYNC_SKIP_NO_ACTIVITY = 5,          /* :231-236 */
+  CDR_SYNC_SKIP_LOCAL_VERSION_LARGER = 6, /* :238-241 */
+  CDR_SYNC_SKIP_LOCAL_ATTEMPT_LARGER = 7, /* :244-247 */
+  CDR_SYNC_SKIP_HEARTBEAT_OLDER = 8,      /* :248-253 */
+  CDR_SYNC_APPLIED = 9,                   /* :261-294 the request updated the row */
+  CDR_SYNC_E_STATE = 10 /* the addressed record's result.code != CDR_OK, or wf >= n_states: nothing
+                           is read from the record and nothing is written */
+};
+#define CDR_SYNC_RESET_TIMER_STATUS 0x1u /* resetActivityTimerTaskStatus was true (:265-270) */
+#define CDR_SYNC_HAS_TIMER_TASK 0x2u     /* GetActivityTimerTaskIfNeeded created timer_task (:289-291) */
+#define CDR_SYNC_NO_ROW 0xFFFFFFFFu
+
+/* Per request.  Fields that do not apply are zero (rows: CDR_SYNC_NO_ROW).  The builder kind
+ * of a loaded state is read from its records: 2DC when repl.present is set, else NDC when
+ * exec.flags has CDR_XI_VH_BRANCH or the state has version-history items, else local.
+ * `code` is CDR_OK except for the two failures of the walk, where `action` names the exit
+ * that raised it: CDR_P_UNKNOWN_WF_STATE (action SKIP_NOT_RUNNING) and CDR_E_VH_EMPTY —
+ * GetLastWriteVersion on an NDC state without version-history items,
+ * mutableStateBuilder.go:526-545 (action SKIP_STALE_VERSION).  Nothing is written to the
+ * state for either. */
+typedef struct cdr_sync_result {
+  int32_t action; /* cdr_sync_action */
+  int32_t code;   /* cdr_status */
+  uint32_t flags; /* CDR_SYNC_* (APPLIED only) */
+  uint32_t _pad;
+  int64_t next_event_id;      /* the state's; the retry hint, and for APPLIED the Condition of the
+                                 passive update (every action but NO_WORKFLOW / E_STATE) */
+  int64_t event_time;         /* APPLIED: max(scheduled, started, last heartbeat) of the request, the
+                                 `now` of updateWorkflowExecutionAsPassive (:277-294) */
+  int64_t last_write_version; /* with next_event_id; CDR_EMPTY_VERSION where GetLastWriteVersion fails */
+  /* absolute row indices into state->act — the rows the caller must upsert: act_row the synced
+   * row, task_row the row whose timer_task_status gained a bit (it can be another activity) */
+  uint32_t act_row, task_row;
+  uint64_t tag;
+  uint64_t _pad1;
+  /* CDR_SYNC_HAS_TIMER_TASK: type CDR_TT_ACTIVITY_TIMEOUT with timeout_type, event_id =
+   * ScheduleID, visibility_ts and attempt; version 0, left to the caller as for the
+   * stateBuilder's tasks */
+  cdr_task timer_task;
+} cdr_sync_result;
+#ifdef __cplusplus
+static_assert(sizeof(cdr_sync_activity) == 64, "cdr_sync_activity");
+static_assert(sizeof(cdr_sync_result) == 128 && offsetof(cdr_sync_result, timer_task) == 64, "cdr_sync_result");
+#endif
 
 /* ==================================================== NDC VERSION HISTORIES ===
  * The persisted VersionHistories of an NDC workflow (common/persistence/versionHistory.go:
