@@ -117,9 +117,14 @@ __device__ bool parse_uuid(const Strs& S, uint32_t h, uint8_t* u) {
   }
   return k == 32;
 }
-// a binary field of MustParseUUID(string of h): absent for "", CDR_BLOB_E_UUID where Go panics
+// a binary field of MustParseUUID(string of h): absent for "", CDR_BLOB_E_UUID where Go panics;
+// a handle past the table is CDR_BLOB_E_HANDLE, whatever the field's type
 __device__ void uuid_bin_f(Out& o, const Strs& S, uint32_t id, uint32_t h) {
-  if (S.len(h) == 0 && S.ok(h)) return;
+  if (!S.ok(h)) {
+    o.err = o.err ? o.err : CDR_BLOB_E_HANDLE;
+    return;
+  }
+  if (S.len(h) == 0) return;
   uint8_t u[16];
   if (!parse_uuid(S, h, u)) {
     o.err = o.err ? o.err : CDR_BLOB_E_UUID;
@@ -245,12 +250,18 @@ __device__ void version_histories(Out& o, const Strs& S, const cdr_exec_info& x,
   o.b(0);
 }
 // byte range [m0, m1) of Memo field 10 (map<string, binary>) inside the Memo struct body
-// handle h holds; false when absent (err set when the body is not a Memo struct)
+// handle h holds; false when absent (err set when the body is not a Memo struct: it ends
+// before its stop byte, a field before the map is not a string, or the map's 2 * count
+// length-prefixed items do not all lie inside the body)
 __device__ bool memo_fields(const Strs& S, uint32_t h, uint64_t& m0, uint64_t& m1, int32_t& err) {
+  if (!S.ok(h)) {
+    err = err ? err : CDR_BLOB_E_HANDLE;
+    return false;
+  }
   const uint64_t n = S.len(h);
-  const uint8_t* s = S.ok(h) ? S.at(h) : nullptr;
+  const uint8_t* s = S.at(h);
   uint64_t p = 0;
-  while (s && p < n) {
+  while (p < n) {
     const uint32_t t = s[p];
     if (t == 0) return false;
     if (p + 3 > n) break;
@@ -260,8 +271,9 @@ __device__ bool memo_fields(const Strs& S, uint32_t h, uint64_t& m0, uint64_t& m
       if (p + 6 > n) break;
       const uint32_t cnt = rd_be32(s + p + 2);
       uint64_t q = p + 6;
-      for (uint64_t e = 0; e < 2ull * cnt && q + 4 <= n; e++) q += 4 + rd_be32(s + q);
-      if (q > n) break;
+      uint64_t e = 0;
+      for (; e < 2ull * cnt && q + 4 <= n; e++) q += 4 + rd_be32(s + q);
+      if (e < 2ull * cnt || q > n) break;  // an item's length or bytes past the body
       m0 = p, m1 = q;
       return true;
     }
@@ -428,13 +440,18 @@ struct Cql {
   }
   __device__ void lit(const char* s, uint32_t n) { o.be32(n), o.lit(s, n); }
   // uuid from a Go string: gocql ParseUUID (a '-' where an even number of hex digits has
-  // been read is skipped; exactly 32 hex digits) — CDR_BLOB_E_UUID where it fails
+  // been read is skipped; exactly 32 hex digits) — CDR_BLOB_E_UUID where it fails,
+  // CDR_BLOB_E_HANDLE for a handle past the table
   __device__ void uuid_str(uint32_t h) {
     uint8_t u[16] = {};
+    if (!S.ok(h)) {
+      o.err = o.err ? o.err : CDR_BLOB_E_HANDLE;
+      return null();
+    }
     const uint64_t n = S.len(h);
     const uint8_t* s = S.at(h);
     uint32_t j = 0;
-    bool ok = S.ok(h);
+    bool ok = true;
     for (uint64_t i = 0; ok && i < n; i++) {
       const uint32_t c = s[i];
       if (c == '-' && (j & 1) == 0) continue;

@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass, field
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -519,12 +520,14 @@ class Engine:
             C.memmove(out.tables[t], getattr(v, t), C.sizeof(TABLE_TYPES[t]) * getattr(pl.totals, t))
         return out
 
-    def encode_rows(self, batch: Batch, out: Outputs, table: str) -> bytes:
+    def encode_rows(self, batch: Batch, out: Outputs, table: str, fill: int = 0) -> bytes:
         """sqlblobs row blobs of one pending table ("timer" or "cancel") of replayed
         outputs through cdr_encode_rows_async (the records go to HBM, the blobs come
         back): blob of row r in the slot at r * CDR_BLOB_*_STRIDE, returned as
         {row: blob bytes} for the rows of OK entries.  Device memory through the HIP
-        runtime directly (the context this engine already initialised)."""
+        runtime directly (the context this engine already initialised).  `fill`: the byte
+        the slot buffer is pre-filled with; `self.encoded.raw` keeps the whole buffer as it
+        came back (tests: the slots the call must leave untouched)."""
         tid, size, stride = {"timer": (1, 45, 48), "cancel": (3, 66, 80)}[table]
         hip = _hip()
         pl = out.plan
@@ -552,7 +555,7 @@ class Engine:
             o.result = up(out.result)
             setattr(o, table, up(out.tables[table]))
             blobs = dalloc(n_rows * stride)
-            hip.hipMemset(blobs, 0, C.c_size_t(n_rows * stride))
+            hip.hipMemset(blobs, fill, C.c_size_t(n_rows * stride))
             rc = abi.lib().cdr_encode_rows_async(self.ctx, tid, C.byref(db), C.byref(o), blobs, None)
             if rc:
                 raise RuntimeError(f"cdr_encode_rows_async rc={rc}")
@@ -560,6 +563,7 @@ class Engine:
             if hip.hipMemcpy(host, blobs, C.c_size_t(n_rows * stride), 2) != 0:  # DeviceToHost (synchronises)
                 raise RuntimeError("hipMemcpy D2H failed")
             raw = bytes(host)
+            self.encoded = SimpleNamespace(raw=raw, stride=stride, n_rows=n_rows, row_off=None, status=None)
             off = {"timer": "timer_off", "cancel": "cancel_off"}[table]
             cnt = {"timer": "n_timer", "cancel": "n_cancel"}[table]
             blobs_out = {}
@@ -576,14 +580,20 @@ class Engine:
                 hip.hipFree(p)
 
     def encode_blobs(self, batch: Batch, out: Outputs, table: str, strings: list, persist=None,
-                     cluster_names=None, form: str = "sql"):
+                     cluster_names=None, form: str = "sql", fill: int = 0, guard: int = 0,
+                     with_status: bool = True):
         """Variable-size sqlblobs row blobs through cdr_encode_blobs_async (size pass +
         scan, then the write pass) for table "act", "child", "signal" or "exec", with
         `strings[h]` (bytes) the string table: ({row: blob}, {row: CDR_BLOB_* status}) for
         the rows of OK entries (exec: row = entry).  `persist` is a cdr_exec_persist array
         and `cluster_names` a list of handles (table "exec").  form="cql": the Cassandra
         form instead (cdr_encode_cql_async: each row's CQL bound values), tables "act",
-        "timer", "child", "cancel", "signal", "exec"."""
+        "timer", "child", "cancel", "signal", "exec".
+        `fill` / `guard`: the write pass goes into a buffer pre-filled with the byte `fill`
+        with `guard` more such bytes on both sides of [0, total) (so `blobs` points `guard`
+        bytes into its allocation); both guards are checked on return.  with_status=False
+        passes NULL for row_status (the statuses come back empty).  `self.encoded` keeps
+        the raw row_off array (n_rows + 1), the status array and the blob bytes."""
         tid = {"act": 0, "timer": 1, "child": 2, "cancel": 3, "signal": 4, "exec": 5}[table]
         fn = "cdr_encode_cql_async" if form == "cql" else "cdr_encode_blobs_async"
         hip = _hip()
@@ -632,7 +642,7 @@ class Engine:
             pp = up(persist) if persist is not None else None
             cn = up((C.c_uint32 * max(1, len(cluster_names or [])))(*(cluster_names or [])))
             row_off = dalloc(8 * (n_rows + 1))
-            status = dalloc(4 * n_rows)
+            status = dalloc(4 * n_rows) if with_status else None
             L = abi.lib()
             rc = getattr(L, fn)(self.ctx, tid, C.byref(db), C.byref(o), C.byref(st), pp, cn, n_rows,
                                 row_off, None, status, None)
@@ -640,13 +650,20 @@ class Engine:
                 raise RuntimeError(f"{fn} (sizes) rc={rc}")
             offs = np.frombuffer(down(row_off, 8 * (n_rows + 1)), np.uint64)
             total = int(offs[-1])
-            blobs = dalloc(total)
+            buf = dalloc(total + 2 * guard)
+            if hip.hipMemset(buf, fill, C.c_size_t(max(8, total + 2 * guard))) != 0:
+                raise RuntimeError("hipMemset failed")
+            blobs = C.c_void_p(buf.value + guard)
             rc = getattr(L, fn)(self.ctx, tid, C.byref(db), C.byref(o), C.byref(st), pp, cn, n_rows,
                                 row_off, blobs, status, None)
             if rc:
                 raise RuntimeError(f"{fn} (write) rc={rc}")
-            raw = down(blobs, total)
-            stat = np.frombuffer(down(status, 4 * n_rows), np.int32)
+            whole = down(buf, total + 2 * guard)
+            if whole[:guard] != bytes([fill]) * guard or whole[guard + total:] != bytes([fill]) * guard:
+                raise RuntimeError(f"{fn}: the write pass stored outside [0, row_off[n_rows])")
+            raw = whole[guard:guard + total]
+            stat = np.frombuffer(down(status, 4 * n_rows), np.int32) if with_status else None
+            self.encoded = SimpleNamespace(raw=raw, row_off=offs, status=stat, n_rows=n_rows, stride=None)
             got, codes = {}, {}
             cnt = {"act": "n_activity", "timer": "n_timer", "child": "n_child", "cancel": "n_cancel",
                    "signal": "n_signal"}.get(table)
@@ -657,7 +674,8 @@ class Engine:
                                                      for j in range(getattr(out.result[w], cnt))]
                 for r in rows:
                     got[r] = raw[int(offs[r]):int(offs[r + 1])]
-                    codes[r] = int(stat[r])
+                    if stat is not None:
+                        codes[r] = int(stat[r])
             return got, codes
         finally:
             for p in ptrs:

@@ -604,6 +604,8 @@ typedef struct cdr_exec_persist {
   uint32_t client_library_version, client_feature_version, client_impl, _pad;
 } cdr_exec_persist;
 #define CDR_ZERO_TIME_NANOS (-6795364578871345152ll) /* time.Time{}.UnixNano() */
+/* A handle >= strs->n is CDR_BLOB_E_HANDLE in every field that reads it, UUID-typed and Memo
+ * fields included (nothing is parsed); a row with a status != 0 has unspecified bytes. */
 #define CDR_BLOB_OK 0
 #define CDR_BLOB_E_UUID 1   /* MustParseUUID would panic on the string */
 #define CDR_BLOB_E_HANDLE 2 /* a handle past the string table */

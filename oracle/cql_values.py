@@ -39,6 +39,10 @@ class BadUUID(ValueError):
     pass
 
 
+BadHandle = tb.BadHandle  # a handle past the string table, whatever the column's type
+BadMemo = tb.BadMemo      # the Memo handle's bytes do not parse (tb._memo_fields)
+
+
 def val(b: bytes | None) -> bytes:
     """A CQL [bytes] value: int32 length + bytes; None is null (length -1)."""
     return struct.pack(">i", -1) if b is None else struct.pack(">i", len(b)) + b

@@ -80,6 +80,25 @@ class BadUUID(ValueError):
     """sqldb.MustParseUUID would panic (common/persistence/sql/storage/sqldb/uuid.go:39-45)."""
 
 
+class BadHandle(ValueError):
+    """A handle past the string table (cdr.h CDR_BLOB_E_HANDLE), whatever the field's type."""
+
+
+class BadMemo(ValueError):
+    """The Memo handle's bytes do not parse as a Memo struct body (cdr.h CDR_BLOB_E_MEMO)."""
+
+
+def lookup(strings):
+    """S(handle) -> bytes over a handle table held as a list: BadHandle past its end."""
+    n = len(strings)
+
+    def S(h: int) -> bytes:
+        if not 0 <= h < n:
+            raise BadHandle(h)
+        return strings[h]
+    return S
+
+
 def double(fid: int, v: float) -> bytes:
     return field(T_DOUBLE, fid, struct.pack(">d", v))
 
@@ -198,24 +217,38 @@ def version_histories_blob(token: bytes, items) -> bytes:
 
 
 def _memo_fields(body: bytes) -> bytes | None:
-    """The map body of Memo field 10 inside a Memo struct body (None if absent)."""
-    p = 0
+    """The map body of Memo field 10 inside a Memo struct body (None if absent).  Every
+    read is bounds-checked: BadMemo where the body ends before its stop byte, a field
+    before the map is not a string, or the map's 2 x count length-prefixed items do not
+    all lie inside the body."""
+    n, p = len(body), 0
+
+    def be32(q):
+        if q + 4 > n:
+            raise BadMemo(f"length at {q} past the body's {n} bytes")
+        return struct.unpack(">I", body[q:q + 4])[0]
     while True:
+        if p >= n:
+            raise BadMemo("no stop byte")
         t = body[p]
         if t == 0:
             return None
+        if p + 3 > n:
+            raise BadMemo("field header cut")
         fid = struct.unpack(">h", body[p + 1:p + 3])[0]
         p += 3
         if t == T_MAP and fid == 10:
+            if p + 6 > n:
+                raise BadMemo("map header cut")
             q = p + 6
-            n = struct.unpack(">i", body[p + 2:p + 6])[0]
-            for _ in range(2 * n):
-                q += 4 + struct.unpack(">i", body[q:q + 4])[0]
+            for _ in range(2 * be32(p + 2)):
+                q += 4 + be32(q)
+                if q > n:
+                    raise BadMemo(f"map item runs to {q}, past the body's {n} bytes")
             return body[p:q]
-        if t in (T_STRING,):
-            p += 4 + struct.unpack(">i", body[p:p + 4])[0]
-        else:
-            raise ValueError(f"unexpected Memo field type {t}")
+        if t != T_STRING:
+            raise BadMemo(f"unexpected Memo field type {t}")
+        p += 4 + be32(p)
 
 
 def exec_info_blob(x, builder, S, persist, repl=None, vh_items=(), rps=None, sa=None, cluster_names=()) -> bytes:

@@ -19,6 +19,7 @@ import pytest
 
 from cadence_amd import abi, engine
 from tests import mutation_ref as ref
+from tests.states import make_state
 
 TABLES = ref.TABLES
 FILL = 0xA5
@@ -152,29 +153,6 @@ CASES = [("sizes", 0, 0, 1), ("sparse", "in_long"), ("sizes", 0, 1, 1), ("sizes"
          ("sizes", 65, 63, 100), ("sizes", 129, 0, 129), ("sizes", 0, 129, 129)]
 
 
-def _state(per_entry, slack):
-    """Outputs holding per_entry[w][table] rows, entry w's slices slack(w) rows larger."""
-    n = len(per_entry)
-    caps = (abi.CdrWfCaps * n)()
-    tot = abi.CdrTotals()
-    for w, tabs in enumerate(per_entry):
-        for t in TABLES:
-            setattr(caps[w], t + "_off", getattr(tot, t))
-            setattr(caps[w], t + "_cap", len(tabs[t]) + slack(w))
-            setattr(tot, t, getattr(tot, t) + len(tabs[t]) + slack(w))
-    fake = engine.Batch(events=(abi.CdrEvent * 0)(), wfs=(abi.CdrWfDesc * n)(), kvs=(abi.CdrKV * 0)(),
-                        rps=(abi.CdrResetPoint * 0)(), cluster=engine.default_cluster())
-    st = engine.Outputs(fake, engine.Plan(caps=caps, totals=tot))
-    for w, tabs in enumerate(per_entry):
-        st.exec[w].next_event_id = 1000 + 7 * w
-        for t in TABLES:
-            setattr(st.result[w], engine.TABLE_COUNT[t], len(tabs[t]))
-            off = getattr(caps[w], t + "_off")
-            for j, r in enumerate(tabs[t]):
-                st.tables[t][off + j] = r
-    return fake, st
-
-
 def _hand_made(entries, src=None):
     """(batch, out) of hand-made entries [(IN tables, OUT tables)]: loaded record src[w]
     (default: the records in reverse order) and entry w's replayed state."""
@@ -184,8 +162,8 @@ def _hand_made(entries, src=None):
     for w, (tin, _) in enumerate(entries):
         if src[w] >= 0:
             ins[src[w]] = tin
-    _, st_in = _state(ins, lambda w: w % 3)
-    batch, st_out = _state([tout for _, tout in entries], lambda w: (w + 1) % 4)
+    _, st_in = make_state(ins, lambda w: w % 3)
+    batch, st_out = make_state([tout for _, tout in entries], lambda w: (w + 1) % 4)
     batch.carry = engine.Carry(src=src, state=st_in)
     return batch, st_out
 
