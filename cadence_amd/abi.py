@@ -295,6 +295,11 @@ SLAB_COLS = (("event_id", np.int64), ("version", np.int64), ("timestamp", np.int
 EL_BYTES = sum(np.dtype(t).itemsize for _, t in SLAB_COLS)  # CDR_EL_BYTES
 SEF_BATCH_FIRST, SEF_DOMAIN_MISSING = 1 << 8, 1 << 9
 SEF_ID_NEXT, SEF_VER_SAME = 1 << 21, 1 << 22  # delta bits (cdr.h)
+SEF_NEED_TS, SEF_NEED_KEY, SEF_NEED_AUX, SEF_NEED_H, SEF_NEED_N = (1 << b for b in range(16, 21))
+# operand hint fields (cdr.h): key == event_id - d (d = 1..7); aux == 0 (7) or event_id - d (d = 1..6)
+SEF_KEY_BACK_SHIFT, SEF_AUX_IMPL_SHIFT = 10, 13
+SEF_KEY_BACK, SEF_AUX_IMPL = 7 << SEF_KEY_BACK_SHIFT, 7 << SEF_AUX_IMPL_SHIFT
+SEF_AUX_ZERO = 7
 
 
 ROW_BYTES = EL_BYTES * SLICE_WIDTH  # CDR_ROW_BYTES

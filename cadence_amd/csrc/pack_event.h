@@ -169,7 +169,8 @@ CDR_HD void cdr_put_event(uint8_t* row, uint32_t i, const cdr_event* ep, bool fi
       default:
         break;
     }
-    tf[i] = cdr_type_flags(e.type, flags);
+    const uint32_t tfw = cdr_type_flags(e.type, flags);
+    tf[i] = tfw | cdr_operand_hints(tfw, e.event_id, kk, ax);  // operand hints (cdr.h): the cells keep their values
     eid[i] = e.event_id;
     ver[i] = e.version;
     ts[i] = e.timestamp;

@@ -289,7 +289,9 @@ __device__ __forceinline__ uint32_t gate(uint32_t off, uint32_t tf, uint32_t bit
 }
 // DELTA: skip the event_id / version loads the packer's CDR_SEF_ID_NEXT / VER_SAME bits
 // make redundant (the consumer rebuilds them, ev_delta)
-template <bool DELTA = false, int AUX = 0>
+// HINT: skip the key / aux loads the packer's operand hint fields (CDR_SEF_KEY_BACK /
+// CDR_SEF_AUX_IMPL) make redundant (the consumer rebuilds them from the event's id, ev_hint)
+template <bool DELTA = false, int AUX = 0, bool HINT = false>
 __device__ __forceinline__ Ev load_ops(const Slice& S, uint32_t o8, uint32_t tf) {
   const uint32_t o4 = o8 - S.l4;
   Ev e;
@@ -298,8 +300,10 @@ __device__ __forceinline__ Ev load_ops(const Slice& S, uint32_t o8, uint32_t tf)
   e.ver = bld64<AUX>(S.r, DELTA ? o8 | ((tf & CDR_SEF_VER_SAME) ? OOB_BIT : 0u) : o8, S.col(CDR_COL_VERSION));
 #if CDR_TYPED
   e.ts = bld64<AUX>(S.r, gate(o8, tf, CDR_SEF_NEED_TS), S.col(CDR_COL_TIMESTAMP));
-  e.key = bld64<AUX>(S.r, gate(o8, tf, CDR_SEF_NEED_KEY), S.col(CDR_COL_KEY));
-  e.aux = bld64<AUX>(S.r, gate(o8, tf, CDR_SEF_NEED_AUX), S.col(CDR_COL_AUX));
+  e.key = bld64<AUX>(S.r, gate(o8, tf, CDR_SEF_NEED_KEY) | ((HINT && (tf & CDR_SEF_KEY_BACK)) ? OOB_BIT : 0u),
+                     S.col(CDR_COL_KEY));
+  e.aux = bld64<AUX>(S.r, gate(o8, tf, CDR_SEF_NEED_AUX) | ((HINT && (tf & CDR_SEF_AUX_IMPL)) ? OOB_BIT : 0u),
+                     S.col(CDR_COL_AUX));
   e.h = bld32<AUX>(S.r, gate(o4, tf, CDR_SEF_NEED_H), S.col(CDR_COL_H));
   e.n = (int32_t)bld32<AUX>(S.r, gate(o4, tf, CDR_SEF_NEED_N), S.col(CDR_COL_N));
 #else
@@ -310,6 +314,15 @@ __device__ __forceinline__ Ev load_ops(const Slice& S, uint32_t o8, uint32_t tf)
   e.n = (int32_t)bld32<AUX>(S.r, o4, S.col(CDR_COL_N));
 #endif
   return e;
+}
+// the key / aux operands the hint fields of e.tf imply, from the event's final id (the
+// hinted columns were not loaded: load_ops<.., HINT>)
+__device__ __forceinline__ void ev_hint(Ev& e) {
+  const uint32_t kb = (e.tf & CDR_SEF_KEY_BACK) >> CDR_SEF_KEY_BACK_SHIFT;
+  const uint32_t ai = (e.tf & CDR_SEF_AUX_IMPL) >> CDR_SEF_AUX_IMPL_SHIFT;
+  e.key = kb ? (int64_t)((uint64_t)e.id - kb) : e.key;
+  // (aux == 0: the skipped load already returned it)
+  e.aux = (ai && ai != CDR_SEF_AUX_ZERO) ? (int64_t)((uint64_t)e.id - ai) : e.aux;
 }
 
 // ---------------------------------------------------------------- working slots
@@ -2680,7 +2693,11 @@ int cdr_replay_sliced_async(cdr_ctx* c, const cdr_dev_batch* in, const cdr_out* 
     HIPCHK(hipEventRecord(c->ev[1], st));
   }
   const uint32_t fb = (in->n_wfs + 255) / 256;
-  if (fb) hipLaunchKernelGGL(k_tables, dim3(fb), dim3(256), 0, st, *in, *out);
+  // a launch of fast slices alone (no other class, no loaded state, no retry lists) needs no
+  // table epilogue: a fast entry has at most one pending activity, emitted live at its slot, no
+  // other table rows, and k_replay_fast writes its SearchAttributes in key order
+  const bool all_fast = fst && kinds == 1 && in->n_fast_slices == blocks && gf.x == blocks && !carry && !rws;
+  if (fb && !all_fast) hipLaunchKernelGGL(k_tables, dim3(fb), dim3(256), 0, st, *in, *out);
   HIPCHK(hipGetLastError());
   if (fb) hipLaunchKernelGGL(k_finalize, dim3(fb), dim3(256), 0, st, *in, *out);
   HIPCHK(hipGetLastError());
@@ -2694,7 +2711,7 @@ uint32_t cdr_build_flags(void) {
 #ifdef CDR_PAR_PROF
   f |= 1u;
 #endif
-  if (CDR_PAR_PRIO != 0 || CDR_FDEPTH != 2 || CDR_DEPTH != 1 || CDR_TYPED != 1 || CDR_FAST_DELTA != 1 ||
+  if (CDR_PAR_PRIO != 0 || CDR_FDEPTH != 2 || CDR_DEPTH != 1 || CDR_TYPED != 1 || CDR_FAST_DELTA != 1 || CDR_FAST_HINT != 1 ||
       CDR_VHBF != 1 || CDR_VHQUICK != 1 || CDR_CLS_DEPTH != 1 || CDR_CLS_PDEPTH != 4 || CDR_CLS_DEPTH_PAR != 4 ||
       CDR_CLS_PDEPTH_PAR != 16 || CDR_WPE_FAST != 3 || CDR_WPE != 3 || CDR_WPE_CLS != 4 || CDR_WPE_CLS0 != 4 ||
       CDR_WPE_CLS2 != 2 || FAST_CK != 8u || CDR_FAST_TBUF != 5 || CDR_WPE_FAST_TBUF != 2)

@@ -41,6 +41,10 @@ constexpr uint32_t FD = CDR_FDEPTH;
 #ifndef CDR_FAST_DELTA
 #define CDR_FAST_DELTA 1 /* skip event_id / version loads the delta bits make redundant */
 #endif
+#ifndef CDR_FAST_HINT
+#define CDR_FAST_HINT 1 /* skip key / aux loads the operand hint fields make redundant (0: load as before) */
+#endif
+#define FAST_LOAD_OPS load_ops<CDR_FAST_DELTA, CDR_NT_FAST, CDR_FAST_HINT != 0>
 // copy a landed prefetch slot out through an opaque move, so that the register
 // allocator cannot merge the copy with the slot (which would move the slot's refill
 // into fresh registers and copy it back, waiting on the refill, at the loop latch)
@@ -312,16 +316,17 @@ k_replay_fast(cdr_launch L) {
 #pragma unroll
   for (uint32_t j = 0; j < FD; j++) T[j] = load_tf<CDR_NT_FAST>(S, el8(j, len, lane));
 #pragma unroll
-  for (uint32_t j = 0; j < FD; j++) Q[j] = load_ops<CDR_FAST_DELTA, CDR_NT_FAST>(S, el8(j, len, lane), T[j]);
+  for (uint32_t j = 0; j < FD; j++) Q[j] = FAST_LOAD_OPS(S, el8(j, len, lane), T[j]);
 #pragma unroll
   for (uint32_t j = 0; j < FD; j++) T[j] = load_tf<CDR_NT_FAST>(S, el8(j + FD, len, lane));
   const uint32_t srows = S.elems / CDR_SLICE_WIDTH;
   {  // ---- event 0: WorkflowExecutionStarted on every lane (CDR_CAP_FAST), peeled so
      // that its temporaries do not add to the replay loop's register pressure
     const uint32_t k = 0;
-    const Ev e = ev_take(Q[0]);
+    Ev e = ev_take(Q[0]);
+    if (CDR_FAST_HINT) ev_hint(e);  // (an entry's first event carries no delta bit: its id was loaded)
     const uint32_t tn = tf_take(T[0]);
-    Q[0] = load_ops<CDR_FAST_DELTA, CDR_NT_FAST>(S, el8(k + FD, len, lane), tn);
+    Q[0] = FAST_LOAD_OPS(S, el8(k + FD, len, lane), tn);
     T[0] = load_tf<CDR_NT_FAST>(S, el8(k + 2 * FD, len, lane));
     call_first_id = SEL(!done, e.id, call_first_id);
     prev_id = SEL(done, prev_id, e.id);
@@ -443,7 +448,18 @@ k_replay_fast(cdr_launch L) {
         if (af & CDR_SF_HAS_SEARCH_ATTR) {
           const uint32_t off = a->search_attr_off, cnt = a->search_attr_len, cap = CP.sa_cap;
           f_cap |= cnt > cap;
-          for (uint32_t q = 0; q < cnt && q < cap; q++) gput(sa + nsa++, gget(gp(B_.kvs) + (off + q)));
+          // each row at its rank among the input keys (ascending, equal keys in input order):
+          // k_tables' order, so that a launch of fast slices alone needs no k_tables pass
+          nsa = cnt < cap ? cnt : cap;
+          for (uint32_t q = 0; q < nsa; q++) {
+            const cdr_kv kv = gget(gp(B_.kvs) + (off + q));
+            uint32_t rank = 0;
+            for (uint32_t j = 0; j < nsa; j++) {
+              const uint32_t kj = gp(B_.kvs)[off + j].key;
+              rank += (kj < kv.key || (kj == kv.key && j < q)) ? 1u : 0u;
+            }
+            gput(sa + rank, kv);
+          }
           xf |= nsa ? CDR_XI_HAS_SEARCH_ATTR : 0u;
         }
       }
@@ -478,7 +494,7 @@ k_replay_fast(cdr_launch L) {
   auto step = [&](const uint32_t k, Ev& q, uint32_t& t) __attribute__((always_inline)) {
     Ev e = ev_take(q);
     const uint32_t tn = tf_take(t);
-    q = load_ops<CDR_FAST_DELTA, CDR_NT_FAST>(S, el8q(k + FD), tn);
+    q = FAST_LOAD_OPS(S, el8q(k + FD), tn);
     t = load_tf<CDR_NT_FAST>(S, el8q(k + 2 * FD));
     const uint32_t type = e.tf & 0xFFu;
 #if CDR_FAST_QROW
@@ -562,6 +578,7 @@ k_replay_fast(cdr_launch L) {
       }
     }
     }  // the general row
+    if (CDR_FAST_HINT) ev_hint(e);  // key / aux the packer marked as implied by the event's id (cdr.h)
     // ---- dispatch: one pass per distinct event type among the lanes still replaying
     for (uint64_t pend = __builtin_amdgcn_ballot_w64(!done); pend;) {
       uint32_t ut = __builtin_amdgcn_readlane(type, __builtin_ctzll(pend));

@@ -29,7 +29,8 @@ def encoded_event_bytes(tf) -> int:
     """Bytes of the packed input the fast kernel must read for these events (type_flags
     column `tf`, padding cells excluded): the 4-B type word, event_id / version unless the
     packer's delta bits imply them (CDR_SEF_ID_NEXT / VER_SAME), the operand columns the
-    type's need bits name, and the arena record of WorkflowExecutionStarted /
+    type's need bits name (key / aux unless an operand hint field implies them,
+    CDR_SEF_KEY_BACK / AUX_IMPL), and the arena record of WorkflowExecutionStarted /
     ActivityTaskScheduled.  The canonical SURVEY §8(d) price (48 + A[type]) assumes every
     core column is read; this is what the encoding leaves to read."""
     tf = np.asarray(tf)
@@ -37,8 +38,10 @@ def encoded_event_bytes(tf) -> int:
     real = ty < abi.EV["UpsertWorkflowSearchAttributes"] + 1
     b = np.full(tf.shape, 4, np.int64)
     b += np.where(tf & abi.SEF_ID_NEXT, 0, 8) + np.where(tf & abi.SEF_VER_SAME, 0, 8)
-    for bit, w in ((1 << 16, 8), (1 << 17, 8), (1 << 18, 8), (1 << 19, 4), (1 << 20, 4)):  # CDR_SEF_NEED_*
-        b += np.where(tf & bit, w, 0)
+    # CDR_SEF_NEED_*; a key / aux column the operand hint fields imply is not read
+    for bit, w, hint in ((abi.SEF_NEED_TS, 8, 0), (abi.SEF_NEED_KEY, 8, abi.SEF_KEY_BACK),
+                         (abi.SEF_NEED_AUX, 8, abi.SEF_AUX_IMPL), (abi.SEF_NEED_H, 4, 0), (abi.SEF_NEED_N, 4, 0)):
+        b += np.where((tf & bit != 0) & (tf & hint == 0), w, 0)
     b += np.where(ty == abi.EV["WorkflowExecutionStarted"], C.sizeof(abi.AttrStarted), 0)
     b += np.where(ty == abi.EV["ActivityTaskScheduled"], C.sizeof(abi.AttrATSched), 0)
     return int(b[real].sum())

@@ -57,7 +57,9 @@ extern "C" {
  * each column of a step as one coalesced 256/512-B access and a whole step from one
  * contiguous 3.75 KB row (DRAM-page friendly), and one buffer descriptor per slice
  * addresses every column with an immediate column offset.  The kernel reads only the
- * operand columns an event's type needs (CDR_SEF_NEED_* bits of type_flags).
+ * operand columns an event's type needs (CDR_SEF_NEED_* bits of type_flags); the
+ * fast-path kernel also skips a key / aux cell the event's id implies (CDR_SEF_KEY_BACK /
+ * CDR_SEF_AUX_IMPL below).
  *
  * Operand columns per type (all others 0):
  *   WorkflowExecutionStarted  aux = arena word offset of cdr_attr_wf_started
@@ -162,6 +164,21 @@ typedef struct cdr_slices {
  * registers */
 #define CDR_SEF_ID_NEXT (1u << 21)
 #define CDR_SEF_VER_SAME (1u << 22)
+/* operand hint fields (set by the packer from the event's own values, only when the
+ * type's need bit for that column is set): the key / aux operand follows from the
+ * event's id, as Cadence writes history (a DecisionTaskStarted follows its Scheduled,
+ * Started and Completed are flushed together, attempt is 0 outside transient decisions).
+ *   CDR_SEF_KEY_BACK  0 = none; d = 1..7: key == event_id - d
+ *   CDR_SEF_AUX_IMPL  0 = none; 7: aux == 0; else d = 1..6: aux == event_id - d
+ * (uint64_t arithmetic, wrapping, like the delta bits; aux == 0 takes 7 whatever the
+ * id).  The columns still hold the full values; the fast-path kernel skips loading a
+ * hinted column and rebuilds the operand from the event's id (replay.hip ev_hint), every
+ * other reader ignores the fields. */
+#define CDR_SEF_KEY_BACK_SHIFT 10
+#define CDR_SEF_KEY_BACK (7u << CDR_SEF_KEY_BACK_SHIFT)
+#define CDR_SEF_AUX_IMPL_SHIFT 13
+#define CDR_SEF_AUX_IMPL (7u << CDR_SEF_AUX_IMPL_SHIFT)
+#define CDR_SEF_AUX_ZERO 7u
 /* operand columns the event's type reads (set by the packer from CDR_NEED_*) */
 #define CDR_SEF_NEED_TS (1u << 16)
 #define CDR_SEF_NEED_KEY (1u << 17)
@@ -206,6 +223,22 @@ CDR_HD uint32_t cdr_type_flags(uint32_t type, uint32_t flags) {
           ((CDR_NEED_N & b) ? CDR_SEF_NEED_N : 0u);
   }
   return tf;
+}
+/* the operand hint fields of an event whose type_flags word (need bits) is tf */
+CDR_HD uint32_t cdr_operand_hints(uint32_t tf, int64_t event_id, int64_t key, int64_t aux) {
+  uint32_t hints = 0;
+  if (tf & CDR_SEF_NEED_KEY) {
+    const uint64_t d = (uint64_t)event_id - (uint64_t)key;
+    if (d >= 1 && d <= 7) hints |= (uint32_t)d << CDR_SEF_KEY_BACK_SHIFT;
+  }
+  if (tf & CDR_SEF_NEED_AUX) {
+    const uint64_t d = (uint64_t)event_id - (uint64_t)aux;
+    if (aux == 0)
+      hints |= CDR_SEF_AUX_ZERO << CDR_SEF_AUX_IMPL_SHIFT;
+    else if (d >= 1 && d <= 6)
+      hints |= (uint32_t)d << CDR_SEF_AUX_IMPL_SHIFT;
+  }
+  return hints;
 }
 
 /* everything the device needs for one replay launch (all pointers device memory) */
