@@ -44,6 +44,15 @@ constexpr uint32_t FD = CDR_FDEPTH;
 #ifndef CDR_FAST_HINT
 #define CDR_FAST_HINT 1 /* skip key / aux loads the operand hint fields make redundant (0: load as before) */
 #endif
+#ifndef CDR_FAST_UNI
+#define CDR_FAST_UNI 1 /* the uniform loop: groups of rows whose type_flags are the same on every lane take their gates, hints and dispatch from a scalar (0: the per-lane loop alone) */
+#endif
+#ifndef CDR_FAST_UNI_SKIP
+#define CDR_FAST_UNI_SKIP 1 /* the uniform loop issues only the loads its row needs, scalar branches round the others (0: every load, an unneeded one through a descriptor of no records) */
+#endif
+// which instantiation of the step a loop runs (a tag: the step is a generic lambda)
+struct fast_uni_no { static constexpr bool value = false; };
+struct fast_uni_yes { static constexpr bool value = true; };
 #define FAST_LOAD_OPS load_ops<CDR_FAST_DELTA, CDR_NT_FAST, CDR_FAST_HINT != 0>
 // copy a landed prefetch slot out through an opaque move, so that the register
 // allocator cannot merge the copy with the slot (which would move the slot's refill
@@ -480,46 +489,32 @@ k_replay_fast(cdr_launch L) {
   }
   // one replay step over row k from its prefetch slot (rows past the slice are OOB
   // loads of zero on lanes already done: the tail group needs no guard)
+  const uint32_t lane8 = lane * 8u;
 #if CDR_FAST_SADDR
   // the loop's row offsets: the row index clamped to the slice (a scalar), plus the lane's
   // element offset — a lane past its own history reads the slice's padding cells (type
   // CDR_EV_PAD, no operand column needed) and is `done` anyway; no per-lane bounds select
-  const uint32_t lane8 = lane * 8u;
   auto el8q = [&](uint32_t kk) {
     return __builtin_amdgcn_readfirstlane((kk < srows ? kk : srows - 1u) * CDR_ROW_BYTES) + lane8;
   };
 #else
   auto el8q = [&](uint32_t kk) { return el8(kk, len, lane); };
 #endif
-  auto step = [&](const uint32_t k, Ev& q, uint32_t& t) __attribute__((always_inline)) {
-    Ev e = ev_take(q);
-    const uint32_t tn = tf_take(t);
-    q = FAST_LOAD_OPS(S, el8q(k + FD), tn);
-    t = load_tf<CDR_NT_FAST>(S, el8q(k + 2 * FD));
-    const uint32_t type = e.tf & 0xFFu;
-#if CDR_FAST_QROW
-    // the quick row: every lane of the wave still replaying, inside its history, and its event
-    // carrying both delta bits (id = previous + 1, version = previous).  Then the version
-    // prelude's checks pass and add no item (the VHQUICK argument below), CurrentVersion is
-    // already this version (the previous event set it while the state was Created / Running,
-    // and the state only moves forward), and nothing can end a lane before the dispatch — so
-    // the step's bookkeeping is the call boundary alone, with no `done` guard on any of it
-    const int64_t qid = (int64_t)((uint64_t)prev_id + 1u);
-    const bool qlane = !done && k < len && (e.tf & CDR_SEF_ID_NEXT) && (e.tf & CDR_SEF_VER_SAME) &&
-                       (!isVH || (n_vh != 0 && qid >= 0));
-    if (__builtin_amdgcn_ballot_w64(!qlane) == 0) {
-      e.id = qid;
-      e.ver = prev_ver;
-      const bool bf = (e.tf & CDR_SEF_BATCH_FIRST) != 0;  // call boundary (stateBuilder.go:603-604)
-      x_next_event = SEL(bf, qid, x_next_event);
-      call_first_id = SEL(bf, qid, call_first_id);
-      call_first_k = SEL(bf, k, call_first_k);
-      ld = SEL(bf, 0u, ld);
-      prev_id = qid;
-      vh_last_id = SEL(isVH, qid, vh_last_id);
-    } else
+#if CDR_FAST_UNI
+  // the uniform step's loads: the row in soffset (a scalar, clamped to the slice like el8q:
+  // the range check does not see soffset), the lane's element of the column in a loop-invariant
+  // voffset; a column the row does not need is not loaded (its field is zero, as an out-of-range
+  // load leaves it) or, with CDR_FAST_UNI_SKIP 0, read through a descriptor of no records (every
+  // offset out of range: zero, no memory touched).  Skipping makes the compiler's vmcnt count
+  // conservative (a group waits for every load issued before it) and still measured faster
+#if !CDR_FAST_UNI_SKIP
+  const rsrc_t r_none = __builtin_amdgcn_make_buffer_rsrc((void*)(KA()->B.ev.slab + row0 * CDR_ROW_BYTES), (short)0, 0, 0x00020000);
+  auto rs = [&](bool need) { return need ? S.r : r_none; };
 #endif
-    {
+  auto rowq = [&](uint32_t kk) { return __builtin_amdgcn_readfirstlane((kk < srows ? kk : srows - 1u) * CDR_ROW_BYTES); };
+#endif
+  // the general row of a step: delta bits, call boundary and version prelude, per lane
+  auto general_row = [&](Ev& e, const uint32_t k) __attribute__((always_inline)) {
     // event_id / version the packer marked as implied by the previous event (cdr.h)
     e.id = (e.tf & CDR_SEF_ID_NEXT) ? (int64_t)((uint64_t)prev_id + 1u) : e.id;
     e.ver = (e.tf & CDR_SEF_VER_SAME) ? prev_ver : e.ver;
@@ -577,14 +572,121 @@ k_replay_fast(cdr_launch L) {
       vh_last_id = SEL(done, vh_last_id, e.id);
       }
     }
-    }  // the general row
+  };
+  // UNI: the row's type_flags word and the one that gates the next loads are the same on every
+  // executing lane (stf, stn: scalars), every lane is inside its history, and k + FD - 1 < srows
+  auto step = [&](auto uni_, const uint32_t k, Ev& q, uint32_t& t, const uint32_t stf, const uint32_t stn)
+      __attribute__((always_inline)) {
+    constexpr bool UNI = decltype(uni_)::value;
+    Ev e;
+    if constexpr (UNI) {
+#if CDR_FAST_UNI
+      e.tf = stf;
+      e.h = mov32(q.h);
+      e.n = (int32_t)mov32((uint32_t)q.n);
+      e.id = mov64(q.id);
+      e.ver = mov64(q.ver);
+      e.ts = mov64(q.ts);
+      e.key = mov64(q.key);
+      e.aux = mov64(q.aux);
+      // the type_flags word first: the loop's uniformity test reads the newest one, and only
+      // this step's operand loads are then younger than it
+      t = bld32<CDR_NT_FAST>(S.r, S.l4 + S.col(CDR_COL_TYPE_FLAGS), rowq(k + 2 * FD));
+      const uint32_t so = rowq(k + FD);
+      const uint32_t kbn = CDR_FAST_HINT ? (stn & CDR_SEF_KEY_BACK) : 0u, ain = CDR_FAST_HINT ? (stn & CDR_SEF_AUX_IMPL) : 0u;
+      q.tf = stn;
+#if CDR_FAST_UNI_SKIP
+#define UNI_LD64(need, c_) ((need) ? bld64<CDR_NT_FAST>(S.r, lane8 + S.col(c_), so) : (int64_t)0)
+#define UNI_LD32(need, c_) ((need) ? bld32<CDR_NT_FAST>(S.r, S.l4 + S.col(c_), so) : 0u)
+#else
+#define UNI_LD64(need, c_) bld64<CDR_NT_FAST>(rs(need), lane8 + S.col(c_), so)
+#define UNI_LD32(need, c_) bld32<CDR_NT_FAST>(rs(need), S.l4 + S.col(c_), so)
+#endif
+      q.id = UNI_LD64(!(CDR_FAST_DELTA && (stn & CDR_SEF_ID_NEXT)), CDR_COL_EVENT_ID);
+      q.ver = UNI_LD64(!(CDR_FAST_DELTA && (stn & CDR_SEF_VER_SAME)), CDR_COL_VERSION);
+      q.ts = UNI_LD64((stn & CDR_SEF_NEED_TS) != 0, CDR_COL_TIMESTAMP);
+      q.key = UNI_LD64((stn & CDR_SEF_NEED_KEY) && !kbn, CDR_COL_KEY);
+      q.aux = UNI_LD64((stn & CDR_SEF_NEED_AUX) && !ain, CDR_COL_AUX);
+      q.h = UNI_LD32((stn & CDR_SEF_NEED_H) != 0, CDR_COL_H);
+      q.n = (int32_t)UNI_LD32((stn & CDR_SEF_NEED_N) != 0, CDR_COL_N);
+#undef UNI_LD64
+#undef UNI_LD32
+#endif
+    } else {
+      e = ev_take(q);
+      const uint32_t tn = tf_take(t);
+      q = FAST_LOAD_OPS(S, el8q(k + FD), tn);
+      t = load_tf<CDR_NT_FAST>(S, el8q(k + 2 * FD));
+    }
+    const uint32_t type = e.tf & 0xFFu;
+    if constexpr (UNI) {
+      // the quick row from the scalar word: the delta bits are a scalar test and the call
+      // boundary a scalar branch; what remains per lane is `done` and the version-history part
+      const int64_t qid = (int64_t)((uint64_t)prev_id + 1u);
+      const bool qlane = !done && (!isVH || (n_vh != 0 && qid >= 0));
+      if (CDR_FAST_QROW && (stf & CDR_SEF_ID_NEXT) && (stf & CDR_SEF_VER_SAME) && __builtin_amdgcn_ballot_w64(!qlane) == 0) {
+        e.id = qid;
+        e.ver = prev_ver;
+        if (stf & CDR_SEF_BATCH_FIRST) {  // call boundary (stateBuilder.go:603-604)
+          x_next_event = qid;
+          call_first_id = qid;
+          call_first_k = k;
+          ld = 0u;
+        }
+        prev_id = qid;
+        vh_last_id = SEL(isVH, qid, vh_last_id);
+      } else {
+        general_row(e, k);
+      }
+      if (CDR_FAST_HINT) {  // ev_hint with scalar distances
+        const uint32_t kb = (stf & CDR_SEF_KEY_BACK) >> CDR_SEF_KEY_BACK_SHIFT;
+        const uint32_t ai = (stf & CDR_SEF_AUX_IMPL) >> CDR_SEF_AUX_IMPL_SHIFT;
+        if (kb) e.key = (int64_t)((uint64_t)e.id - kb);
+        if (ai && ai != CDR_SEF_AUX_ZERO) e.aux = (int64_t)((uint64_t)e.id - ai);
+      }
+    } else {
+#if CDR_FAST_QROW
+    // the quick row: every lane of the wave still replaying, inside its history, and its event
+    // carrying both delta bits (id = previous + 1, version = previous).  Then the version
+    // prelude's checks pass and add no item (the VHQUICK argument below), CurrentVersion is
+    // already this version (the previous event set it while the state was Created / Running,
+    // and the state only moves forward), and nothing can end a lane before the dispatch — so
+    // the step's bookkeeping is the call boundary alone, with no `done` guard on any of it
+    const int64_t qid = (int64_t)((uint64_t)prev_id + 1u);
+    const bool qlane = !done && k < len && (e.tf & CDR_SEF_ID_NEXT) && (e.tf & CDR_SEF_VER_SAME) &&
+                       (!isVH || (n_vh != 0 && qid >= 0));
+    if (__builtin_amdgcn_ballot_w64(!qlane) == 0) {
+      e.id = qid;
+      e.ver = prev_ver;
+      const bool bf = (e.tf & CDR_SEF_BATCH_FIRST) != 0;  // call boundary (stateBuilder.go:603-604)
+      x_next_event = SEL(bf, qid, x_next_event);
+      call_first_id = SEL(bf, qid, call_first_id);
+      call_first_k = SEL(bf, k, call_first_k);
+      ld = SEL(bf, 0u, ld);
+      prev_id = qid;
+      vh_last_id = SEL(isVH, qid, vh_last_id);
+    } else
+#endif
+    {
+      general_row(e, k);
+    }
     if (CDR_FAST_HINT) ev_hint(e);  // key / aux the packer marked as implied by the event's id (cdr.h)
+    }
     // ---- dispatch: one pass per distinct event type among the lanes still replaying
-    for (uint64_t pend = __builtin_amdgcn_ballot_w64(!done); pend;) {
-      uint32_t ut = __builtin_amdgcn_readlane(type, __builtin_ctzll(pend));
-      asm volatile("" : "+s"(ut));
-      const bool mine = !done && type == ut;
-      pend &= ~__builtin_amdgcn_ballot_w64(mine);
+    // (UNI: the one type is a scalar already, entered once; `mine` is every lane still replaying)
+    for (uint64_t pend = UNI ? 1u : __builtin_amdgcn_ballot_w64(!done); pend;) {
+      uint32_t ut;
+      bool mine;
+      if constexpr (UNI) {
+        ut = type;
+        mine = !done;
+        pend = 0;
+      } else {
+        ut = __builtin_amdgcn_readlane(type, __builtin_ctzll(pend));
+        asm volatile("" : "+s"(ut));
+        mine = !done && type == ut;
+        pend &= ~__builtin_amdgcn_ballot_w64(mine);
+      }
       switch (ut) {
         case CDR_EV_DT_SCHEDULED:  // mutableStateDecisionTaskManager.go:143-167
           dv = SEL(mine, e.ver, dv);
@@ -831,11 +933,39 @@ k_replay_fast(cdr_launch L) {
   // whole groups of FD steps with no exit between them: a skipped step would be a
   // path on which a slot's refill is the newest load, and the waitcnt pass would then
   // wait for everything at every slot use
-  for (uint32_t k = 1; k < srows; k += FD) {  // slot of row k is k % FD
+  uint32_t k = 1;
+#if CDR_FAST_UNI
+  // The uniform loop: whole groups whose rows carry one type_flags word on every executing lane
+  // (the flagship shape: every history of the slice alike).  A group qualifies when the FD words
+  // its steps consume and the FD words that gate their loads each equal the first executing
+  // lane's, every lane's history reaches the group's last row, and that row is inside the slice
+  // (so the group's steps never see a clamped row).  The first group that does not qualify goes
+  // to the loop below, at its boundary, with the ring as that loop keeps it; the uniform loop is
+  // not entered again.  (A uniform step stores the scalar it gated its loads with as the slot's
+  // Q[].tf, so from the second group on only the T[] half of the test can fail: a row that is not
+  // uniform is seen FD rows ahead, as the word that would gate its loads, and the per-lane loop
+  // takes over one group before that row.  The Q[].tf half decides the first group, whose words
+  // the Started block and the prologue loaded per lane.)
+  for (; k + FD <= srows; k += FD) {
+    uint32_t stf[FD], stn[FD];
+    bool nu = k + FD > len;
+#pragma unroll
+    for (uint32_t j = 0; j < FD; j++) {
+      stf[j] = __builtin_amdgcn_readfirstlane(Q[(1 + j) % FD].tf);
+      stn[j] = __builtin_amdgcn_readfirstlane(T[(1 + j) % FD]);
+      nu |= Q[(1 + j) % FD].tf != stf[j] || T[(1 + j) % FD] != stn[j];
+    }
+    if (__builtin_amdgcn_ballot_w64(nu) != 0 || __builtin_amdgcn_ballot_w64(!done) == 0) break;
+    step(fast_uni_yes{}, k, Q[1 % FD], T[1 % FD], stf[0], stn[0]);
+    if (FD > 1) step(fast_uni_yes{}, k + 1, Q[2 % FD], T[2 % FD], stf[1 % FD], stn[1 % FD]);
+    if (FD > 2) step(fast_uni_yes{}, k + 2, Q[3 % FD], T[3 % FD], stf[2 % FD], stn[2 % FD]);
+  }
+#endif
+  for (; k < srows; k += FD) {  // slot of row k is k % FD
     if (__builtin_amdgcn_ballot_w64(!done) == 0) break;
-    step(k, Q[1 % FD], T[1 % FD]);
-    if (FD > 1) step(k + 1, Q[2 % FD], T[2 % FD]);
-    if (FD > 2) step(k + 2, Q[3 % FD], T[3 % FD]);
+    step(fast_uni_no{}, k, Q[1 % FD], T[1 % FD], 0u, 0u);
+    if (FD > 1) step(fast_uni_no{}, k + 1, Q[2 % FD], T[2 % FD], 0u, 0u);
+    if (FD > 2) step(fast_uni_no{}, k + 2, Q[3 % FD], T[3 % FD], 0u, 0u);
   }
 #undef PFAIL
 #undef SEL
