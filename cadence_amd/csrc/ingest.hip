@@ -300,7 +300,7 @@ struct Ctx {  // per launch
   // pass outputs
   uint32_t* counts;   // COUNT: [4 * n_blobs] events, kvs, rps, strings
   unsigned long long* totals;  // COUNT: string fields, failed blobs
-  const uint64_t* bases;  // FILL: [3 * n_blobs] event, kv, rp bases
+  const uint64_t* bases;  // FILL: [3 * n_blobs] event, kv, rp bases (and `counts`: the rows each blob owns)
   int32_t* status;
   cdr_event* events;
   cdr_kv* kvs;
@@ -313,6 +313,9 @@ struct Blob {
   Rd r;
   uint32_t n_ev = 0, n_kv = 0, n_rp = 0, n_str = 0;
   uint64_t ev0 = 0, kv0 = 0, rp0 = 0;
+  // FILL: the rows pass 1 counted for this blob.  A repeated field keeps its last
+  // occurrence, so an earlier, longer occurrence walks past them: every store checks
+  uint32_t lim_ev = 0, lim_kv = 0, lim_rp = 0;
 
   __device__ __forceinline__ Blob(const Ctx& c, uint32_t b) : C(c) {
     r.init(c.bytes, c.blob_off[b], c.blob_off[b + 1], c.total);
@@ -320,6 +323,10 @@ struct Blob {
       ev0 = c.bases[3ull * b];
       kv0 = c.bases[3ull * b + 1];
       rp0 = c.bases[3ull * b + 2];
+      const uint4 n = *reinterpret_cast<const uint4*>(c.counts + 4ull * b);
+      lim_ev = n.x;
+      lim_kv = n.y;
+      lim_rp = n.z;
     }
   }
 
@@ -370,25 +377,26 @@ struct Blob {
       f(ft, fid);
     }
   }
-  __device__ __forceinline__ int64_t i64(uint32_t ft) {
-    if (ft != T_I64) {
+  __device__ __forceinline__ void i64(uint32_t ft, int64_t* v) {
+    if (ft != T_I64) {  // ignored: an earlier occurrence stays
       skip1(r, ft);
-      return 0;
+      return;
     }
-    return (int64_t)r.be64();
+    *v = (int64_t)r.be64();
   }
   // name of a WorkflowType / TaskList / ActivityType (field 10)
-  __device__ __forceinline__ uint32_t name_of(uint32_t ft) {
+  // (a field of another wire type is ignored: an earlier occurrence stays)
+  __device__ __forceinline__ void name_of(uint32_t ft, uint32_t* name) {
     if (ft != T_STRUCT) {
       skip1(r, ft);
-      return 0;
+      return;
     }
     uint32_t h = 0;
     fields([&](uint32_t t, uint32_t id) {
       if (id == 10 && t == T_STRING) h = str();
       else skip1(r, t);
     });
-    return h;
+    *name = h;
   }
   // shared.WorkflowExecution{10 workflowId, 20 runId}
   __device__ __forceinline__ void execution(uint32_t ft, uint32_t* wid, uint32_t* rid) {
@@ -396,6 +404,7 @@ struct Blob {
       skip1(r, ft);
       return;
     }
+    *wid = *rid = 0;  // a repeated struct field is replaced whole
     fields([&](uint32_t t, uint32_t id) {
       if (id == 10 && t == T_STRING) *wid = str();
       else if (id == 20 && t == T_STRING) *rid = str();
@@ -404,7 +413,12 @@ struct Blob {
   }
   // RetryPolicy (shared.thrift RetryPolicy): the fields the record keeps
   template <class A>
-  __device__ __forceinline__ void retry(A& a) {
+  __device__ __forceinline__ void retry(A& a, bool again) {
+    if (again) {  // a repeated RetryPolicy is replaced whole
+      a.retry_initial_s = a.retry_max_interval_s = a.retry_max_attempts = a.retry_expiration_s = 0;
+      a.backoff_coefficient = 0.0;
+      a.nonretriable = 0;
+    }
     fields([&](uint32_t t, uint32_t id) {
       if (id == 10 && t == T_I32) a.retry_initial_s = (int32_t)r.be32();
       else if (id == 20 && t == T_DOUBLE) a.backoff_coefficient = __longlong_as_double((long long)r.be64());
@@ -420,44 +434,53 @@ struct Blob {
       } else skip1(r, t);
     });
   }
-  // SearchAttributes{10: map<string, binary>} -> kv rows; returns the pair count
-  __device__ __forceinline__ uint32_t search_attrs(uint32_t* off) {
-    uint32_t cnt = 0;
+  // SearchAttributes{10: map<string, binary>} -> kv rows at *off, *len of them.  *len is the
+  // count of an earlier occurrence in this event (0: none), whose rows are dropped: a record
+  // keeps one SearchAttributes, and they are the blob's last rows so far
+  __device__ __forceinline__ void search_attrs(uint32_t* off, uint32_t* len) {
+    n_kv -= *len;
+    *len = 0;
     *off = (uint32_t)(kv0 + n_kv);
     fields([&](uint32_t t, uint32_t id) {
       if (id != 10 || t != T_MAP) {
         skip1(r, t);
         return;
       }
+      n_kv -= *len;  // a repeated map replaces the pairs read so far
+      *len = 0;
       const uint32_t kt = r.u8(), vt = r.u8();
       const int32_t n = r.size();
       for (int32_t i = 0; i < n && r.ok(); i++) {
         if (kt == T_STRING && vt == T_STRING) {
           const uint32_t k = str(), v = str();
-          if (P == FILL) C.kvs[kv0 + n_kv] = cdr_kv{k, v};
+          if (P == FILL && n_kv < lim_kv) C.kvs[kv0 + n_kv] = cdr_kv{k, v};
           n_kv++;
-          cnt++;
+          (*len)++;
         } else {  // not a map<string, binary>: thriftrw reads no entries
           skip1(r, kt);
           skip1(r, vt);
         }
       }
     });
-    return cnt;
   }
   // ResetPoints{10: list<ResetPointInfo>} -> reset-point rows; false when field 10 is absent
+  // (*len on entry: the rows of an earlier occurrence in this event, dropped like the kv rows)
   __device__ __forceinline__ bool reset_points(uint32_t* off, uint32_t* len) {
     bool have = false;
-    *off = (uint32_t)(rp0 + n_rp);
+    n_rp -= *len;
     *len = 0;
+    *off = (uint32_t)(rp0 + n_rp);
     fields([&](uint32_t t, uint32_t id) {
       if (id != 10 || t != T_LIST) {
         skip1(r, t);
         return;
       }
+      n_rp -= *len;  // a repeated list replaces the points read so far
+      *len = 0;
       const uint32_t et = r.u8();
       const int32_t n = r.size();
-      if (et != T_STRUCT) {  // not a list of structs: no points
+      if (et != T_STRUCT) {  // not a list of structs: no points (thriftrw assigns nil)
+        have = false;
         for (int32_t i = 0; i < n && r.ok(); i++) skip1(r, et);
         return;
       }
@@ -481,10 +504,10 @@ struct Blob {
             p.expiring_time_nano = (int64_t)r.be64();
             p.flags |= CDR_RP_HAS_EXPIRING;
           } else if (id2 == 60 && t2 == T_BOOL) {
-            p.flags |= CDR_RP_HAS_RESETTABLE | (r.u8() ? CDR_RP_RESETTABLE : 0u);
+            p.flags = (p.flags & ~CDR_RP_RESETTABLE) | CDR_RP_HAS_RESETTABLE | (r.u8() ? CDR_RP_RESETTABLE : 0u);
           } else skip1(r, t2);
         });
-        if (P == FILL) C.rps[rp0 + n_rp] = p;
+        if (P == FILL && n_rp < lim_rp) C.rps[rp0 + n_rp] = p;
         n_rp++;
         (*len)++;
       }
@@ -496,13 +519,13 @@ struct Blob {
   __device__ __forceinline__ void started(cdr_attr_wf_started& s) {
     fields([&](uint32_t t, uint32_t id) {
       switch (id) {
-        case 10: s.workflow_type = name_of(t); break;
+        case 10: name_of(t, &s.workflow_type); break;
         case 12:
           if (t == T_STRING) {
             bool miss;
-            s.flags |= CDR_SF_HAS_PARENT_DOMAIN;
             s.parent_domain_id = domain_id(str(), &miss);
-            s.flags |= miss ? CDR_SF_PARENT_DOMAIN_MISSING : 0u;
+            s.flags = (s.flags & ~CDR_SF_PARENT_DOMAIN_MISSING) | CDR_SF_HAS_PARENT_DOMAIN |
+                      (miss ? CDR_SF_PARENT_DOMAIN_MISSING : 0u);
           } else skip1(r, t);
           break;
         case 14:
@@ -515,21 +538,23 @@ struct Blob {
             s.parent_initiated_id = (int64_t)r.be64();
           } else skip1(r, t);
           break;
-        case 20: s.task_list = name_of(t); break;
+        case 20: name_of(t, &s.task_list); break;
         case 40: if (t == T_I32) s.exec_timeout_s = (int32_t)r.be32(); else skip1(r, t); break;
         case 50: if (t == T_I32) s.task_timeout_s = (int32_t)r.be32(); else skip1(r, t); break;
         case 54: if (t == T_STRING) s.continued_run_id = str(); else skip1(r, t); break;
         case 55:
           if (t == T_I32) {  // ContinueAsNewInitiator: Decider 0, RetryPolicy 1, CronSchedule 2
             const int32_t v = (int32_t)r.be32();
+            s.flags &= ~(CDR_SF_CRON_INITIATOR | CDR_SF_RETRY_INITIATOR | CDR_SF_DECIDER_INITIATOR);
             s.flags |= CDR_SF_HAS_INITIATOR | (v == 2 ? CDR_SF_CRON_INITIATOR : 0u) |
                        (v == 1 ? CDR_SF_RETRY_INITIATOR : 0u) | (v == 0 ? CDR_SF_DECIDER_INITIATOR : 0u);
           } else skip1(r, t);
           break;
         case 70:
           if (t == T_STRUCT) {
+            const bool again = s.flags & CDR_SF_HAS_RETRY;
             s.flags |= CDR_SF_HAS_RETRY;
-            retry(s);
+            retry(s, again);
           } else skip1(r, t);
           break;
         case 80: if (t == T_I32) s.attempt = (int32_t)r.be32(); else skip1(r, t); break;
@@ -545,13 +570,16 @@ struct Blob {
         case 121:
           if (t == T_STRUCT) {
             s.flags |= CDR_SF_HAS_SEARCH_ATTR;
-            s.search_attr_len = search_attrs(&s.search_attr_off);
+            search_attrs(&s.search_attr_off, &s.search_attr_len);
           } else skip1(r, t);
           break;
         case 130:
           if (t == T_STRUCT) {
             if (reset_points(&s.reset_points_off, &s.reset_points_len)) s.flags |= CDR_SF_HAS_RESET_POINTS;
-            else s.reset_points_off = s.reset_points_len = 0;
+            else {
+              s.reset_points_off = s.reset_points_len = 0;
+              s.flags &= ~CDR_SF_HAS_RESET_POINTS;
+            }
           } else skip1(r, t);
           break;
         default: skip1(r, t); break;
@@ -575,11 +603,11 @@ struct Blob {
         have_dom = true;
       } else if (f_we && id == f_we) execution(t, &x.workflow_id, &x.run_id);
       else if (f_wid && id == f_wid && t == T_STRING) x.workflow_id = str();
-      else if (child && id == 30) x.workflow_type = name_of(t);
+      else if (child && id == 30) name_of(t, &x.workflow_type);
       else if (sig && id == 40 && t == T_STRING) x.signal_name = str();
       else if (f_in && id == f_in && t == T_STRING) x.input = str();
       else if (id == f_ctl && t == T_STRING) x.control = str();
-      else if (f_only && id == f_only && t == T_BOOL) x.flags |= r.u8() ? CDR_XF_CHILD_ONLY : 0u;
+      else if (f_only && id == f_only && t == T_BOOL) x.flags = (x.flags & ~CDR_XF_CHILD_ONLY) | (r.u8() ? CDR_XF_CHILD_ONLY : 0u);
       else if (child && id == 81 && t == T_I32) x.parent_close_policy = (int32_t)r.be32();
       else skip1(r, t);
     });
@@ -620,11 +648,27 @@ struct Blob {
         {310, 50, 40}, {320, 10, 30}, {350, 60, 0},  {360, 20, 30}, {370, 50, 30}, {380, 60, 40},
         {390, 50, 30}, {400, 50, 30}, {410, 40, 20}, {430, 50, 40}, {440, 10, 30},
     };
+    // a repeated attribute struct is replaced whole, and the record's one union holds the
+    // last attribute struct of the event: nothing of an earlier one survives, rows included.
+    // e.flags (set when the event ends) holds the earlier struct's field id meanwhile, so
+    // the usual event, with one attribute struct, pays a compare
+    if (e.flags) {
+      if (e.flags == 40) {
+        n_kv -= e.a.started.search_attr_len;
+        n_rp -= e.a.started.reset_points_len;
+      } else if (e.flags == 450) {
+        n_kv -= e.a.upsert.search_attr_len;
+      }
+      uint64_t* z = reinterpret_cast<uint64_t*>(&e.a);
+#pragma unroll
+      for (uint32_t i = 0; i < sizeof(e.a) / 8; i++) z[i] = 0;
+    }
+    e.flags = attr;
     switch (attr) {
       case 40: started(e.a.started); return;
       case 80:
         fields([&](uint32_t t, uint32_t id) {
-          if (id == 10) e.a.dt_sched.task_list = name_of(t);
+          if (id == 10) name_of(t, &e.a.dt_sched.task_list);
           else if (id == 20 && t == T_I32) e.a.dt_sched.start_to_close_s = (int32_t)r.be32();
           else if (id == 30 && t == T_I64) e.a.dt_sched.attempt = (int64_t)r.be64();
           else skip1(r, t);
@@ -635,14 +679,15 @@ struct Blob {
         fields([&](uint32_t t, uint32_t id) {
           if (id == 10 && t == T_STRING) a.activity_id = str();
           else if (id == 25 && t == T_STRING) a.domain = str();
-          else if (id == 30) a.task_list = name_of(t);
+          else if (id == 30) name_of(t, &a.task_list);
           else if (id == 45 && t == T_I32) a.s2c_s = (int32_t)r.be32();
           else if (id == 50 && t == T_I32) a.s2s_s = (int32_t)r.be32();
           else if (id == 55 && t == T_I32) a.stc_s = (int32_t)r.be32();
           else if (id == 60 && t == T_I32) a.hb_s = (int32_t)r.be32();
           else if (id == 110 && t == T_STRUCT) {
+            const bool again = a.flags & CDR_AF_HAS_RETRY;
             a.flags |= CDR_AF_HAS_RETRY;
-            retry(a);
+            retry(a, again);
           } else skip1(r, t);
         });
         if (a.domain) {  // the target domain's ID (refreshTasks, getTargetDomainID)
@@ -673,7 +718,7 @@ struct Blob {
         return;
       case 450:
         fields([&](uint32_t t, uint32_t id) {
-          if (id == 20 && t == T_STRUCT) e.a.upsert.search_attr_len = search_attrs(&e.a.upsert.search_attr_off);
+          if (id == 20 && t == T_STRUCT) search_attrs(&e.a.upsert.search_attr_off, &e.a.upsert.search_attr_len);
           else skip1(r, t);
         });
         return;
@@ -731,11 +776,11 @@ struct Blob {
     for (uint32_t i = 0; i < sizeof(cdr_event) / 8; i++) z[i] = 0;
     fields([&](uint32_t t, uint32_t id) {
       switch (id) {
-        case 10: e.event_id = i64(t); break;
-        case 20: e.timestamp = i64(t); break;
+        case 10: i64(t, &e.event_id); break;
+        case 20: i64(t, &e.timestamp); break;
         case 30: if (t == T_I32) e.type = r.be32(); else skip1(r, t); break;
-        case 35: e.version = i64(t); break;
-        case 36: e.task_id = i64(t); break;
+        case 35: i64(t, &e.version); break;
+        case 36: i64(t, &e.task_id); break;
         default:
           if (t == T_STRUCT && id >= 40 && id <= 450 && id % 10 == 0) attributes(id, e);
           else skip1(r, t);
@@ -743,7 +788,7 @@ struct Blob {
       }
     });
     e.flags = first ? CDR_EVF_BATCH_FIRST : 0u;
-    if (P == FILL && r.ok()) {
+    if (P == FILL && r.ok() && n_ev < lim_ev) {
       cdr_event* d = C.events + ev0 + n_ev;
       const uint64_t* s = reinterpret_cast<const uint64_t*>(&e);
       uint64_t* o = reinterpret_cast<uint64_t*>(d);
@@ -770,12 +815,13 @@ struct Blob {
       }
       const uint32_t et = r.u8();
       const int32_t n = r.size();
-      if (et != T_STRUCT) {  // not a list of structs: thriftrw reads no events
+      // a repeated field 10 replaces the events read so far (FromWire assigns each occurrence);
+      // the fill pass stores an earlier list's rows only inside this blob's ranges (lim_*)
+      n_ev = n_kv = n_rp = 0;
+      if (et != T_STRUCT) {  // not a list of structs: thriftrw reads no events (assigns nil)
         for (int32_t i = 0; i < n && r.ok(); i++) skip1(r, et);
         return;
       }
-      // a repeated field 10 replaces the events read so far (FromWire assigns each occurrence)
-      n_ev = n_kv = n_rp = 0;
       for (int32_t i = 0; i < n && r.ok(); i++) event(n_ev == 0);
     });
     if (r.ok() && n_ev == 0) r.err = CDR_DEC_NO_EVENTS;

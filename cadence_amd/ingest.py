@@ -113,8 +113,10 @@ class Decoded:
     raw: object = None  # the cdr_ingest_out (device pointers, valid until the context's next ingest)
 
 
-def decode(eng: engine.Engine, enc: Encoded) -> Decoded:
-    """cdr_ingest_decode on the device; host copies of every output."""
+def decode(eng: engine.Engine, enc: Encoded, byte_offset: int = 0) -> Decoded:
+    """cdr_ingest_decode on the device; host copies of every output.  `byte_offset` k:
+    the blob bytes are uploaded k bytes into a larger allocation whose other bytes hold
+    0xA5 and the decoder gets the shifted pointer (blob_bytes need not be aligned)."""
     hip = engine._hip()
     L = abi.lib()
     ptrs = []
@@ -133,11 +135,23 @@ def decode(eng: engine.Engine, enc: Encoded) -> Decoded:
         if n:
             assert hip.hipMemcpy(out.ctypes.data, C.c_void_p(ptr), C.c_size_t(out.nbytes), 2) == 0
         return out[:n]
+
+    def up_shifted(a: np.ndarray, k: int):
+        a = np.ascontiguousarray(a)
+        size = k + a.nbytes + 16
+        p = C.c_void_p()
+        assert hip.hipMalloc(C.byref(p), C.c_size_t(size)) == 0
+        ptrs.append(p)
+        assert hip.hipMemset(p, 0xA5, C.c_size_t(size)) == 0
+        if a.nbytes:
+            assert hip.hipMemcpy(C.c_void_p(p.value + k), a.ctypes.data, C.c_size_t(a.nbytes), 1) == 0
+        return p.value + k
     try:
         sb, so = _table(enc.seeds)
         dm = np.array(enc.domain_map, np.uint32).reshape(-1) if enc.domain_map else np.zeros(2, np.uint32)
         inp = abi.CdrIngestIn()
-        inp.blob_bytes, inp.blob_off, inp.entry_blob0 = up(enc.blob_bytes), up(enc.blob_off), up(enc.entry_blob0)
+        inp.blob_bytes = up_shifted(enc.blob_bytes, byte_offset) if byte_offset else up(enc.blob_bytes)
+        inp.blob_off, inp.entry_blob0 = up(enc.blob_off), up(enc.entry_blob0)
         inp.seed_bytes, inp.seed_off, inp.domain_map = up(sb), up(so), up(dm)
         inp.n_blobs, inp.n_entries = len(enc.blob_off) - 1, len(enc.entry_blob0) - 1
         inp.n_seeds, inp.n_domains = len(enc.seeds), len(enc.domain_map)

@@ -32,6 +32,28 @@
  * list of structs has no events.  The attribute struct present decides the union member
  * (schema.h cdr_event).  Decode failures (missing / wrong preamble, truncated value,
  * nesting deeper than CDR_THRIFT_MAX_DEPTH) are reported per blob and per entry.
+ *
+ * Repeated fields.  A field that occurs again keeps its last occurrence, as FromWire
+ * assigns each occurrence in turn: a scalar or string is overwritten; a struct-valued
+ * field (TaskList, WorkflowExecution, RetryPolicy, SearchAttributes, ResetPoints, an
+ * attribute struct) is replaced whole, so nothing of the earlier occurrence survives; a
+ * repeated list or map of the right field type whose element types are not the IDL's
+ * assigns nil (History.events again as list<i64>: no events).  An occurrence of another
+ * wire type is ignored and an earlier one stays.  The record has one attribute union:
+ * it holds the last attribute struct of the event, whichever member that is.  Rows
+ * (cdr_kv, cdr_reset_point) exist only for what the records keep; strings of replaced
+ * occurrences may still hold handles that no record names.
+ *
+ * Depth.  CDR_THRIFT_MAX_DEPTH bounds the containers (struct, list, set, map) open at
+ * once inside one value the decoder does not walk field by field: an unknown field, a
+ * field of an unexpected wire type, an attribute struct the record form does not keep,
+ * an element of a list or map whose element types are not the IDL's, and the values kept
+ * as raw bytes (Memo, nonRetriableErrorReasons).  The skipped value itself is level 1;
+ * level CDR_THRIFT_MAX_DEPTH + 1 fails with CDR_DEC_DEPTH.  The structs the decoder walks
+ * (History, its event list, HistoryEvent, the attribute structs, TaskList / WorkflowType,
+ * WorkflowExecution, RetryPolicy, SearchAttributes and its map, ResetPoints, its list and
+ * ResetPointInfo) do not count, wherever the skipped value sits in them.  (thriftrw sets
+ * no limit; this one bounds the skipper's stack.)
  */
 #ifndef CDR_INGEST_H
 #define CDR_INGEST_H
@@ -49,7 +71,7 @@ extern "C" {
 #define CDR_DEC_MISSING_VERSION 1 /* empty blob (codec MissingBinaryEncodingVersion) */
 #define CDR_DEC_INVALID_VERSION 2 /* first byte != 0x59 (InvalidBinaryEncodingVersion) */
 #define CDR_DEC_TRUNCATED 3       /* a value runs past the blob */
-#define CDR_DEC_DEPTH 4           /* nesting deeper than CDR_THRIFT_MAX_DEPTH */
+#define CDR_DEC_DEPTH 4           /* a skipped value nests deeper than CDR_THRIFT_MAX_DEPTH (see Depth above) */
 #define CDR_DEC_NO_EVENTS 5       /* a history node without events (applyEvents of an empty history) */
 #define CDR_DEC_BAD_SIZE 6        /* negative length / element count */
 #define CDR_DEC_BAD_TYPE 7        /* a wire type the binary protocol does not define */

@@ -78,9 +78,15 @@ class Reader:
             raise DecodeError(DEC_BAD_SIZE)
         return n
 
-    def value(self, t, depth=0):
+    def value(self, t, depth=0, kind=None):
         """A generic wire value: ints / bytes / ("struct", {id: (type, value, (start, end))}) /
-        ("list", elem type, [values]) / ("map", kt, vt, [(k, v)])."""
+        ("list", elem type, [values]) / ("map", kt, vt, [(k, v)]).
+
+        `kind` names a value the decoder walks field by field (WALK below); None is a
+        value it skips or keeps as raw bytes.  CDR_THRIFT_MAX_DEPTH (cdr/ingest.h) bounds
+        the containers open at once inside one skipped value, that value being level 1:
+        walked containers do not count, and each value skipped from inside one starts
+        again at level 1."""
         if t in FIXED:
             raw = self.take(FIXED[t])
             if t == T_DOUBLE:
@@ -89,8 +95,9 @@ class Reader:
         if t == T_STRING:
             return bytes(self.take(self.size()))
         if t in (T_STRUCT, T_LIST, T_SET, T_MAP):
-            if depth >= MAX_DEPTH:
+            if kind is None and depth >= MAX_DEPTH:
                 raise DecodeError(DEC_DEPTH)
+            depth = depth + 1 if kind is None else 0
             if t == T_STRUCT:
                 fields = []
                 while True:
@@ -99,16 +106,56 @@ class Reader:
                         return ("struct", fields)
                     fid = self.i16()
                     start = self.p
-                    v = self.value(ft, depth + 1)
+                    v = self.value(ft, depth, walked(kind, fid, ft))
                     fields.append((fid, ft, v, (start, self.p)))
             if t in (T_LIST, T_SET):
                 et = self.u8()
                 n = self.size()
-                return ("list", et, [self.value(et, depth + 1) for _ in range(n)])
+                ek = {"events": "event", "points": "point"}.get(kind) if et == T_STRUCT else None
+                out = []
+                for _ in range(n):  # (a count past the bytes ends at the first missing element)
+                    out.append(self.value(et, depth, ek))
+                return ("list", et, out)
             kt, vt = self.u8(), self.u8()
             n = self.size()
-            return ("map", kt, vt, [(self.value(kt, depth + 1), self.value(vt, depth + 1)) for _ in range(n)])
+            out = []
+            for _ in range(n):
+                k = self.value(kt, depth)
+                out.append((k, self.value(vt, depth)))
+            return ("map", kt, vt, out)
         raise DecodeError(DEC_BAD_TYPE)
+
+
+# the values the device parser walks field by field: kind of struct -> {(field id, wire
+# type): kind of that field's value}; everything else is skipped (or kept as raw bytes)
+_NAME, _EXEC = "name", "exec"
+_REF_WE = {310: 40, 320: 30, 360: 30, 370: 30, 380: 40, 390: 30, 400: 30, 410: 20, 430: 40, 440: 30}
+_LEAF_ATTRS = (90, 100, 110, 120, 140, 150, 160, 170, 200, 210, 220, 180, 190, 230, 240, 330, 350)
+WALK = {
+    "history": {(10, T_LIST): "events"},
+    "event": {},
+    "attr40": {(10, T_STRUCT): _NAME, (20, T_STRUCT): _NAME, (14, T_STRUCT): _EXEC, (70, T_STRUCT): "retry",
+               (121, T_STRUCT): "sa", (130, T_STRUCT): "rps"},
+    "attr80": {(10, T_STRUCT): _NAME},
+    "attr130": {(30, T_STRUCT): _NAME, (110, T_STRUCT): "retry"},
+    "attr300": {(30, T_STRUCT): _EXEC}, "attr420": {(30, T_STRUCT): _EXEC}, "attr340": {(30, T_STRUCT): _NAME},
+    "attr450": {(20, T_STRUCT): "sa"},
+    "sa": {(10, T_MAP): "sa_map"}, "rps": {(10, T_LIST): "points"},
+    _NAME: {}, _EXEC: {}, "retry": {}, "point": {},
+}
+for _a in _LEAF_ATTRS:
+    WALK["attr%d" % _a] = {}
+for _a, _f in _REF_WE.items():
+    WALK["attr%d" % _a] = {(_f, T_STRUCT): _EXEC}
+
+
+def walked(kind, fid, ft):
+    if kind is None:
+        return None
+    if kind == "event":
+        k = "attr%d" % fid
+        return k if ft == T_STRUCT and k in WALK else None
+    return WALK[kind].get((fid, ft))
 
 
 def fget(st, fid, ftype):
@@ -166,7 +213,7 @@ def decode_blobs(data: bytes, blob_off, entry_blob0, seeds: list[bytes], domain_
                 raise DecodeError(DEC_MISSING_VERSION)
             if r.u8() != 0x59:
                 raise DecodeError(DEC_INVALID_VERSION)
-            hist = r.value(T_STRUCT)
+            hist = r.value(T_STRUCT, 0, "history")
             evs = []
             lst = fget(hist, 10, T_LIST)
             if lst is not None and lst[0][1] == T_STRUCT:
@@ -179,7 +226,8 @@ def decode_blobs(data: bytes, blob_off, entry_blob0, seeds: list[bytes], domain_
             parsed.append([])
             status.append(e.code)
     it = Interner(seeds)
-    dom = {name: ident for name, ident in domain_map}
+    # (name handle, ID handle) among the seeds (cdr/ingest.h): a name past them names nothing
+    dom = {name: ident for name, ident in domain_map if name < len(seeds)}
 
     # every kept string, in a first walk (the same accessors as the fill below)
     def strings_of(events):
@@ -221,6 +269,7 @@ def _event(ev, kvs, rps, data, it, dom, abi, collect=False):
             return 0
         return it.handle(b)
     e = abi.CdrEvent()
+    kv_ev, rp_ev = (len(kvs), len(rps)) if not collect else (0, 0)
     for fid, ft, v, span in ev[1]:
         if fid == 10 and ft == T_I64:
             e.event_id = v
@@ -233,6 +282,11 @@ def _event(ev, kvs, rps, data, it, dom, abi, collect=False):
         elif fid == 36 and ft == T_I64:
             e.task_id = v
         elif ft == T_STRUCT and 40 <= fid <= 450 and fid % 10 == 0:
+            # the record's one union holds the event's last attribute struct, replaced whole
+            # (cdr/ingest.h, Repeated fields): nothing of an earlier one survives, rows included
+            C.memset(C.addressof(e.a), 0, C.sizeof(e.a))
+            if not collect:
+                del kvs[kv_ev:], rps[rp_ev:]
             _attrs(fid, v, e, S, kvs, rps, data, dom, collect)
     return out if collect else e
 
