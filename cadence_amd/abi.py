@@ -55,6 +55,7 @@ STATUS = {
     20: "E_NDC_RETRY_TASK", 21: "E_NDC_BRANCH_CHANGED", 22: "E_NDC_SAME_VERSION", 23: "E_REBUILD_VH_MISMATCH",
     24: "E_VHS_CAPACITY", 25: "E_VH_EMPTY", 32: "P_ACTIVITY_STARTED_NIL", 33: "P_CHILD_STARTED_NIL",
     34: "P_VH_ITEM_INVALID", 35: "P_UNKNOWN_CLUSTER", 36: "P_UNKNOWN_WF_STATE", 64: "NOT_APPLIED", 65: "NOT_RUN",
+    66: "E_LOAD_ROWS",
 }
 OK = 0
 E_HISTORY_EMPTY = 1
@@ -203,6 +204,22 @@ CdrIngestOut = _S("cdr_ingest_out", [(n, C.c_void_p) for n in (
     ("n_events", u64), ("n_kvs", u64), ("n_rps", u64), ("n_strings", u32), ("n_bad_blobs", u32)])
 DEC_STATUS = {0: "OK", 1: "MISSING_VERSION", 2: "INVALID_VERSION", 3: "TRUNCATED", 4: "DEPTH", 5: "NO_EVENTS",
               6: "BAD_SIZE", 7: "BAD_TYPE"}
+# loading persisted rows (cdr.h cdr_load_rows): row / entry statuses are DEC_STATUS plus these
+E_LOAD_ROWS = 66
+LOAD_E_UUID, LOAD_E_DUP_KEY, LOAD_E_ENTRY_ROWS = 16, 17, 18
+LOAD_MAX_ENTRY_ROWS = 16384
+LOAD_STATUS = {**DEC_STATUS, 16: "E_UUID", 17: "E_DUP_KEY", 18: "E_ENTRY_ROWS"}
+LOAD_TABLES = 5
+STR_REF_SEED, STR_REF_GEN = 1 << 63, 1 << 62
+CdrRowsIn = _S("cdr_rows_in", [
+    ("bytes", C.c_void_p), ("n_bytes", u64), ("blob_off", C.c_void_p * LOAD_TABLES),
+    ("entry_row0", C.c_void_p * LOAD_TABLES), ("key", C.c_void_p * LOAD_TABLES), ("timer_id_off", C.c_void_p),
+    ("act_heartbeat", C.c_void_p), ("seed_bytes", C.c_void_p), ("seed_off", C.c_void_p),
+    ("n_rows", u32 * LOAD_TABLES), ("n_entries", u32), ("n_seeds", u32), ("_pad", u32)])
+CdrRowsOut = _S("cdr_rows_out", [
+    ("state", CdrOut), ("caps", C.c_void_p), ("totals", CdrTotals), ("row_status", C.c_void_p * LOAD_TABLES),
+    ("entry_status", C.c_void_p), ("str_ref", C.c_void_p), ("str_len", C.c_void_p), ("gen_bytes", C.c_void_p),
+    ("n_gen_bytes", u64), ("n_strings", u32), ("n_bad_entries", u32)])
 CdrOpts = _S("cdr_opts", [("plan_mode", u32), ("fast_path", i32), ("reg_path", i32), ("concurrent", i32),
                           ("workspace_bytes", u64)])
 CdrVHToken = _S("cdr_vh_token", [("tree", u32), ("_pad", u32), ("branch_lo", u64), ("branch_hi", u64)])
@@ -359,6 +376,7 @@ MIRRORS = {
     "cdr_opts": CdrOpts, "cdr_ingest_in": CdrIngestIn, "cdr_ingest_out": CdrIngestOut,
     "cdr_mut_info": CdrMutInfo, "cdr_mutation": CdrMutation,
     "cdr_sync_activity": CdrSyncActivity, "cdr_sync_result": CdrSyncResult,
+    "cdr_rows_in": CdrRowsIn, "cdr_rows_out": CdrRowsOut,
 }
 
 # C ABI entry points declared in include/cdr/cdr.h and include/cdr/synth.h
@@ -441,6 +459,10 @@ EXPORTS = {
     "cdr_ingest_decode": (i32, [C.c_void_p, C.POINTER(CdrIngestIn), C.POINTER(CdrIngestOut), C.c_void_p]),
     "cdr_ingest_plan": (i32, [C.c_void_p, C.POINTER(CdrIngestOut), C.POINTER(CdrBatch), u32, C.POINTER(CdrDevBatch),
                               C.c_void_p, C.POINTER(CdrTotals), C.c_void_p]),
+    "cdr_load_rows": (i32, [C.c_void_p, C.POINTER(CdrRowsIn), C.POINTER(CdrRowsOut), C.c_void_p]),
+    "cdr_load_pass_ms": (i32, [C.c_void_p, C.POINTER(C.c_float)]),
+    "cdr_strtab_gather_async": (i32, [C.c_void_p, C.c_void_p, C.c_void_p, u32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]),
     "cdr_synth_encode_history": (i32, [C.POINTER(CdrBatch), C.c_void_p, C.c_void_p, u32, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.POINTER(u64), C.POINTER(u32), i32]),
     "cdr_synth_size": (i32, [C.POINTER(CdrSynthParams), C.POINTER(CdrSynthSizes)]),

@@ -52,6 +52,13 @@ enum cdr_ws_slot {
   WS_MUT_DEL_TIMER, WS_MUT_DEL_CHILD, WS_MUT_DEL_CANCEL, WS_MUT_DEL_SIGNAL, WS_MUT_INFO,
   // cdr_sync_activity_batch (sync.hip): requests, their CSR and results (the states reuse WS_CY_*)
   WS_SYNC_REQ, WS_SYNC_OFF, WS_SYNC_RES,
+  // cdr_load_rows (load.hip): outputs and scratch of their own, so that a later
+  // cdr_ingest_decode leaves a loaded state valid
+  WS_LD_ROWENT, WS_LD_STATUS, WS_LD_DEST, WS_LD_TKEY, WS_LD_FAIL, WS_LD_ESTATUS, WS_LD_RESULT, WS_LD_CAPS,
+  WS_LD_ACT, WS_LD_TIMER, WS_LD_CHILD, WS_LD_CANCEL, WS_LD_SIGNAL, WS_LD_GEN, WS_LD_TABKEY, WS_LD_TABVAL,
+  WS_LD_TABREF, WS_LD_TABLEN, WS_LD_SKEY, WS_LD_SKEY2, WS_LD_SIDX, WS_LD_SIDX2, WS_LD_STRREF, WS_LD_STRLEN,
+  WS_LD_MISC, WS_LD_CCOUNT, WS_LD_COFFS, WS_LD_CTMP, WS_LD_SORTTMP,
+  WS_GATHER_TMP,  // cdr_strtab_gather_async: the offset scan's temporary storage
   WS_NUM
 };
 
@@ -114,6 +121,9 @@ struct cdr_ctx {
   void* hs[HS_NUM] = {};
   uint64_t hs_bytes[HS_NUM] = {};
   cdr_one_host one;
+  // cdr_load_rows: events around the passes of the last load (cdr_load_pass_ms)
+  hipEvent_t ld_ev[5] = {};
+  float ld_ms[4] = {};
 };
 
 // pinned host staging `slot` of at least `bytes` (grow-only; contents undefined); nullptr

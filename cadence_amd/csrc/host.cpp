@@ -1223,6 +1223,8 @@ uint64_t cdr_struct_size(const char* name) {
       {"cdr_mutation", sizeof(cdr_mutation)},
       {"cdr_sync_activity", sizeof(cdr_sync_activity)},
       {"cdr_sync_result", sizeof(cdr_sync_result)},
+      {"cdr_rows_in", sizeof(cdr_rows_in)},
+      {"cdr_rows_out", sizeof(cdr_rows_out)},
   };
   for (const E& e : table)
     if (std::strcmp(e.n, name) == 0) return e.s;

@@ -1,0 +1,788 @@
+// load.hip — on-device decode of the SQL persistence's pending-table row blobs into the
+// loaded-state tables cdr_carry takes (cdr.h "loading persisted rows"): the inverse of
+// encode.hip / encode_var.hip for the five pending tables.
+//
+// One lane per row, one parser template per table (the pass is its parameter, so the passes
+// agree on every byte); each wavefront stages its 64 consecutive rows' bytes in LDS first
+// (thrift_dev.h stage_blobs).  The walk of a row only records where its kept fields are (the
+// last occurrence of each); what a pass does with them comes after the walk:
+//   1. COUNT   row status (wire errors, request-ID text, run-ID length) and the string fields
+//              per row; a failing row lowers its entry's first-failure word (atomicMin of
+//              table, row in entry, status);
+//   2. INTERN  seeds, then the strings of rows whose entry has no failing row, then the
+//              generated run-ID texts; the new strings are ranked by hash (hipcub radix sort);
+//   3. RANK    one lane per row: its slot is entry_row0 + #{rows of the entry with a smaller
+//              key}; equal keys fail the entry (a second failure word: the rank pass reads the
+//              first one while it writes);
+//   4. FILL    each record built in registers and stored whole at its ranked slot.
+// An epilogue, one lane per entry, writes result / caps / entry_status from the failure words
+// and the row ranges alone: it walks no rows.
+#include <hip/hip_runtime.h>
+
+#include <hipcub/hipcub.hpp>
+
+#include <cstdio>
+
+#include "cdr/cdr.h"
+#include "cdr/ingest.h"
+#include "ctx.h"
+#include "thrift_dev.h"
+
+#define HIPCHK(x)                                                                                     \
+  do {                                                                                                \
+    hipError_t _e = (x);                                                                              \
+    if (_e != hipSuccess) {                                                                           \
+      fprintf(stderr, "cdr: %s failed: %s (%s:%d)\n", #x, hipGetErrorString(_e), __FILE__, __LINE__); \
+      return CDR_API_EDEVICE;                                                                         \
+    }                                                                                                 \
+  } while (0)
+
+// bytes of row data staged in LDS per wavefront: 64 ActivityInfo rows (~250 B each) fit
+#ifndef CDR_LOAD_STAGE
+#define CDR_LOAD_STAGE 24576
+#endif
+#define CDR_LOAD_BLOCK 128 /* 2 wavefronts: 48 KiB of LDS per workgroup */
+
+namespace {
+
+extern __shared__ uint4 ld_lds[];
+
+enum Pass { COUNT = 0, INTERN = 1, FILL = 2 };
+constexpr uint64_t GEN_REF = 1ull << 62;
+constexpr unsigned long long NO_FAIL = ~0ull;
+constexpr uint32_t GEN_BYTES = 36;
+
+struct Span {  // a string / binary value's bytes in `bytes`; n = 0: absent or empty
+  uint64_t at;
+  uint32_t n;
+};
+
+struct LCtx {  // per launch (one table)
+  const uint8_t* bytes;
+  uint64_t total;
+  const uint64_t* blob_off;
+  const uint64_t* tid_off;    // table 1: the timer-ID strings
+  const int64_t* key;         // tables 0, 2-4
+  const int64_t* hb;          // table 0: the LastHeartbeatUpdatedTime column
+  const uint32_t* row_entry;  // [n_rows]
+  const uint32_t* row0;       // the table's entry_row0
+  unsigned long long* fail;   // [2 * n_entries]: decode failures, then duplicate keys
+  STab T;
+  int32_t* status;             // [n_rows]
+  unsigned long long* totals;  // COUNT: string fields
+  uint8_t* gen;                // table 2: GEN_BYTES per row
+  const uint32_t* dest;        // FILL: [n_rows] ranked slots
+  void* recs;                  // FILL: the table
+  int64_t* tkey;               // table 1: INTERN writes the ID's hash, FILL reads its handle
+  uint32_t n_rows, n_entries;
+};
+
+__device__ __forceinline__ unsigned long long fail_word(uint32_t table, uint32_t row_in_entry, int32_t status) {
+  return ((unsigned long long)table << 56) | ((unsigned long long)row_in_entry << 8) | (uint32_t)status;
+}
+__device__ __forceinline__ uint32_t umin32(uint32_t a, uint32_t b) { return a < b ? a : b; }
+__device__ __forceinline__ uint64_t umin64(uint64_t a, uint64_t b) { return a < b ? a : b; }
+
+// ---------------------------------------------------------------- field readers
+template <class F>
+__device__ __forceinline__ void fields(Rd& r, F&& f) {  // f(field type, field id) consumes the value
+  while (r.ok()) {
+    const uint32_t ft = r.u8();
+    if (!r.ok() || ft == T_STOP) return;
+    const uint32_t fid = r.be16();
+    if (!r.ok()) return;
+    f(ft, fid);
+  }
+}
+// (a field of another wire type is ignored: an earlier occurrence stays)
+__device__ __forceinline__ void f_i64(Rd& r, uint32_t t, int64_t* v) {
+  if (t == T_I64) *v = (int64_t)r.be64();
+  else skip1(r, t);
+}
+__device__ __forceinline__ void f_i32(Rd& r, uint32_t t, int32_t* v) {
+  if (t == T_I32) *v = (int32_t)r.be32();
+  else skip1(r, t);
+}
+__device__ __forceinline__ void f_bool(Rd& r, uint32_t t, uint32_t* flags, uint32_t bit) {
+  if (t == T_BOOL) *flags = (*flags & ~bit) | (r.u8() ? bit : 0u);
+  else skip1(r, t);
+}
+__device__ __forceinline__ void f_str(Rd& r, uint32_t t, Span* s) {
+  if (t != T_STRING) {
+    skip1(r, t);
+    return;
+  }
+  const uint32_t n = (uint32_t)r.size();
+  if (!r.need(n)) return;
+  *s = Span{r.pos, n};
+  r.pos += n;
+}
+
+// the canonical lowercase RFC 4122 text (8-4-4-4-12) -> hi (first 16 digits), lo
+__device__ __forceinline__ bool parse_uuid(Rd& r, Span s, uint64_t* lo, uint64_t* hi) {
+  if (s.n != 36) return false;
+  uint64_t h = 0, l = 0;
+  bool good = true;
+  uint32_t d = 0;
+  for (uint32_t i = 0; i < 36; i++) {
+    const uint32_t c = r.at(s.at + i);
+    if (i == 8 || i == 13 || i == 18 || i == 23) {
+      good = good && c == '-';
+      continue;
+    }
+    uint32_t v;
+    if (c >= '0' && c <= '9') v = c - '0';
+    else if (c >= 'a' && c <= 'f') v = c - 'a' + 10;
+    else {
+      v = 0;
+      good = false;
+    }
+    if (d < 16) h = (h << 4) | v;
+    else l = (l << 4) | v;
+    d++;
+  }
+  *lo = l;
+  *hi = h;
+  return good;
+}
+// character i of sqldb.UUID(b).String() of the 16 bytes at `at`
+__device__ __forceinline__ uint32_t uuid_char(Rd& r, uint64_t at, uint32_t i) {
+  if (i == 8 || i == 13 || i == 18 || i == 23) return '-';
+  const uint32_t d = i - (i > 8 ? 1u : 0u) - (i > 13 ? 1u : 0u) - (i > 18 ? 1u : 0u) - (i > 23 ? 1u : 0u);
+  const uint32_t b = r.at(at + (d >> 1));
+  const uint32_t nib = (d & 1u) ? (b & 15u) : (b >> 4);
+  return nib < 10 ? '0' + nib : 'a' + (nib - 10);
+}
+__device__ __forceinline__ uint64_t uuid_text_hash(Rd& r, uint64_t at) {  // cdr_str_hash of that text
+  uint64_t h = 0xCBF29CE484222325ull;
+  for (uint32_t i = 0; i < GEN_BYTES; i++) h = (h ^ uuid_char(r, at, i)) * 0x100000001B3ull;
+  h = cdr_mix64(h ^ ((uint64_t)GEN_BYTES * 0x9E3779B97F4A7C15ull));
+  return h ? h : 1u;
+}
+
+// ---------------------------------------------------------------- the rows
+template <int TBL> struct RecOf;
+template <> struct RecOf<0> { typedef cdr_activity_info type; };
+template <> struct RecOf<1> { typedef cdr_timer_info type; };
+template <> struct RecOf<2> { typedef cdr_child_info type; };
+template <> struct RecOf<3> { typedef cdr_cancel_info type; };
+template <> struct RecOf<4> { typedef cdr_signal_info type; };
+
+// what the walk of one row leaves: the record's scalar fields, and where its strings are
+template <int TBL>
+struct Row {
+  typename RecOf<TBL>::type rec;
+  Span sp[4];         // the table's handle fields, in the order of finish()
+  Span uu;            // the request-ID text (tables 2-4)
+  Span run;           // table 2: StartedRunID
+  int64_t started26;  // table 0: StartedTimeNanos (absent: 0)
+
+  __device__ __forceinline__ void parse(Rd& r) {
+    uint64_t* z = reinterpret_cast<uint64_t*>(&rec);
+#pragma unroll
+    for (uint32_t i = 0; i < sizeof(rec) / 8; i++) z[i] = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) sp[i] = Span{0, 0};
+    uu = run = Span{0, 0};
+    started26 = 0;
+    if constexpr (TBL == 0) {  // sqlblobs.ActivityInfo
+      cdr_activity_info& a = rec;
+      fields(r, [&](uint32_t t, uint32_t id) {
+        switch (id) {
+          case 10: f_i64(r, t, &a.version); break;
+          case 12: f_i64(r, t, &a.scheduled_event_batch_id); break;
+          case 18: f_i64(r, t, &a.scheduled_time); break;
+          case 20: f_i64(r, t, &a.started_id); break;
+          case 26: f_i64(r, t, &started26); break;
+          case 28: f_str(r, t, &sp[0]); break;
+          case 30: f_str(r, t, &sp[1]); break;
+          case 32: f_i32(r, t, &a.s2s); break;
+          case 34: f_i32(r, t, &a.s2c); break;
+          case 36: f_i32(r, t, &a.stc); break;
+          case 38: f_i32(r, t, &a.hb); break;
+          case 40: f_bool(r, t, &a.flags, CDR_AI_CANCEL_REQUESTED); break;
+          case 42: f_i64(r, t, &a.cancel_request_id); break;
+          case 44: f_i32(r, t, &a.timer_task_status); break;
+          case 46: f_i32(r, t, &a.attempt); break;
+          case 48: f_str(r, t, &sp[2]); break;
+          case 52: f_bool(r, t, &a.flags, CDR_AI_HAS_RETRY); break;
+          case 54: f_i32(r, t, &a.initial_interval); break;
+          case 56: f_i32(r, t, &a.maximum_interval); break;
+          case 58: f_i32(r, t, &a.maximum_attempts); break;
+          case 60: f_i64(r, t, &a.expiration_time); break;
+          case 62:
+            if (t == T_DOUBLE) a.backoff_coefficient = __longlong_as_double((long long)r.be64());
+            else skip1(r, t);
+            break;
+          case 64:
+            if (t == T_LIST) {  // RetryNonRetryableErrors: the list's bytes; empty / not strings -> 0
+              const uint64_t at = r.pos;
+              const uint32_t et = r.u8();
+              const int32_t cnt = r.size();
+              r.pos = r.ok() ? at : r.pos;
+              skip1(r, T_LIST);
+              if (r.ok()) sp[3] = (et == T_STRING && cnt > 0) ? Span{at, (uint32_t)(r.pos - at)} : Span{0, 0};
+            } else skip1(r, t);
+            break;
+          default: skip1(r, t); break;  // event blobs, encodings, identities, the Retry*Last* fields
+        }
+      });
+    } else if constexpr (TBL == 1) {  // sqlblobs.TimerInfo
+      cdr_timer_info& x = rec;
+      fields(r, [&](uint32_t t, uint32_t id) {
+        switch (id) {
+          case 10: f_i64(r, t, &x.version); break;
+          case 12: f_i64(r, t, &x.started_id); break;
+          case 14: f_i64(r, t, &x.expiry_time); break;
+          case 16: f_i64(r, t, &x.task_id); break;
+          default: skip1(r, t); break;
+        }
+      });
+    } else if constexpr (TBL == 2) {  // sqlblobs.ChildExecutionInfo
+      cdr_child_info& c = rec;
+      fields(r, [&](uint32_t t, uint32_t id) {
+        switch (id) {
+          case 10: f_i64(r, t, &c.version); break;
+          case 12: f_i64(r, t, &c.initiated_event_batch_id); break;
+          case 14: f_i64(r, t, &c.started_id); break;
+          case 20: f_str(r, t, &sp[0]); break;
+          case 22: f_str(r, t, &run); break;
+          case 28: f_str(r, t, &uu); break;
+          case 30: f_str(r, t, &sp[1]); break;
+          case 32: f_str(r, t, &sp[2]); break;
+          case 35: f_i32(r, t, &c.parent_close_policy); break;
+          default: skip1(r, t); break;
+        }
+      });
+    } else if constexpr (TBL == 3) {  // sqlblobs.RequestCancelInfo
+      cdr_cancel_info& c = rec;
+      fields(r, [&](uint32_t t, uint32_t id) {
+        switch (id) {
+          case 10: f_i64(r, t, &c.version); break;
+          case 11: f_i64(r, t, &c.initiated_event_batch_id); break;
+          case 12: f_str(r, t, &uu); break;
+          default: skip1(r, t); break;
+        }
+      });
+    } else {  // sqlblobs.SignalInfo
+      cdr_signal_info& g = rec;
+      fields(r, [&](uint32_t t, uint32_t id) {
+        switch (id) {
+          case 10: f_i64(r, t, &g.version); break;
+          case 11: f_i64(r, t, &g.initiated_event_batch_id); break;
+          case 12: f_str(r, t, &uu); break;
+          case 14: f_str(r, t, &sp[0]); break;
+          case 16: f_str(r, t, &sp[1]); break;
+          case 18: f_str(r, t, &sp[2]); break;
+          default: skip1(r, t); break;
+        }
+      });
+    }
+  }
+};
+
+template <int TBL, int P>
+__global__ __launch_bounds__(CDR_LOAD_BLOCK) void k_rows(LCtx C) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  LDS3 uint4* stage = (LDS3 uint4*)ld_lds + (uint64_t)wv * (CDR_LOAD_STAGE / 16);
+  uint64_t s_lo, s_n;
+  stage_blobs(C.bytes, C.blob_off, C.total, CDR_LOAD_STAGE, C.n_rows, r - lane, lane, stage, &s_lo, &s_n);
+  // the wave's LDS writes complete before any of its lanes reads them (one wave: in order)
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  uint64_t n_str = 0;
+  if (r < C.n_rows) {
+    const uint32_t w = C.row_entry[r];
+    // INTERN: rows whose entry can still succeed; FILL: rows whose entry succeeded
+    const bool live = P == COUNT || (C.fail[w] == NO_FAIL && (P == INTERN || C.fail[C.n_entries + w] == NO_FAIL));
+    if (live) {
+      Rd rd;
+      const uint64_t e = umin64(C.blob_off[r + 1], C.total), p = umin64(C.blob_off[r], e);
+      rd.init(C.bytes, p, e, C.total);
+      rd.sb = (const LDS3 uint8_t*)stage;
+      rd.s_lo = s_lo;
+      rd.s_n = s_n;
+      Row<TBL> x;
+      x.parse(rd);
+      int32_t err = rd.err;
+      // a handle field by pass: counted, interned, or looked up
+      auto H = [&](Span s) -> uint32_t {
+        if (s.n == 0) return 0u;
+        if (P == COUNT) {
+          n_str++;
+          return 0u;
+        }
+        const uint64_t h = rd.hash(s.at, s.n);
+        if (P == INTERN) {
+          tab_insert(C.T, h, s.at, s.n, UNASSIGNED);
+          return 0u;
+        }
+        return tab_lookup(C.T, h);
+      };
+      if (err == CDR_DEC_OK) {
+        if constexpr (TBL == 0) {
+          cdr_activity_info& a = x.rec;
+          a.schedule_id = C.key[r];
+          if (x.started26 != CDR_ZERO_TIME_NANOS) {
+            a.flags |= CDR_AI_STARTED_TIME_SET;
+            a.started_time = x.started26;
+          }
+          const int64_t hb = C.hb[r];
+          a.last_heartbeat_time = hb != CDR_ZERO_TIME_NANOS ? hb : 0;
+          if (a.last_heartbeat_time != 0 && !(a.flags & CDR_AI_STARTED_TIME_SET)) a.flags |= CDR_AI_HEARTBEAT_TIME_SET;
+          a.activity_id = H(x.sp[0]);
+          a.request_id = H(x.sp[1]);
+          a.task_list = H(x.sp[2]);
+          a.nonretriable = H(x.sp[3]);
+        } else if constexpr (TBL == 1) {
+          const uint64_t e2 = umin64(C.tid_off[r + 1], C.total), p2 = umin64(C.tid_off[r], e2);
+          const Span id{p2, (uint32_t)(e2 - p2)};
+          if (P == COUNT) n_str += id.n ? 1u : 0u;
+          if (P == INTERN) {
+            const uint64_t h = id.n ? rd.hash(id.at, id.n) : 0ull;
+            if (id.n) tab_insert(C.T, h, id.at, id.n, UNASSIGNED);
+            C.tkey[r] = (int64_t)h;
+          }
+          if (P == FILL) x.rec.timer_id = (uint32_t)C.tkey[r];
+        } else if constexpr (TBL == 2) {
+          cdr_child_info& c = x.rec;
+          c.initiated_id = C.key[r];
+          if (!parse_uuid(rd, x.uu, &c.create_request_lo, &c.create_request_hi)) err = CDR_LOAD_E_UUID;
+          if (x.run.n != 0 && x.run.n != 16) err = CDR_LOAD_E_UUID;
+          if (err == CDR_DEC_OK) {
+            c.started_workflow_id = H(x.sp[0]);
+            c.domain_name = H(x.sp[1]);
+            c.workflow_type = H(x.sp[2]);
+            if (P == COUNT) n_str += x.run.n ? 1u : 0u;
+            if (P == INTERN) {  // the run ID's text, for k_gen_intern (first byte 0: none)
+              uint32_t* g = reinterpret_cast<uint32_t*>(C.gen + (uint64_t)GEN_BYTES * r);
+              if (x.run.n) {
+                for (uint32_t i = 0; i < GEN_BYTES; i += 4)
+                  g[i >> 2] = uuid_char(rd, x.run.at, i) | (uuid_char(rd, x.run.at, i + 1) << 8) |
+                              (uuid_char(rd, x.run.at, i + 2) << 16) | (uuid_char(rd, x.run.at, i + 3) << 24);
+              } else {
+                g[0] = 0;
+              }
+            }
+            if (P == FILL) c.started_run_id = x.run.n ? tab_lookup(C.T, uuid_text_hash(rd, x.run.at)) : 0u;
+          }
+        } else if constexpr (TBL == 3) {
+          cdr_cancel_info& c = x.rec;
+          c.initiated_id = C.key[r];
+          if (!parse_uuid(rd, x.uu, &c.cancel_request_lo, &c.cancel_request_hi)) err = CDR_LOAD_E_UUID;
+        } else {
+          cdr_signal_info& g = x.rec;
+          g.initiated_id = C.key[r];
+          if (!parse_uuid(rd, x.uu, &g.signal_request_lo, &g.signal_request_hi)) err = CDR_LOAD_E_UUID;
+          if (err == CDR_DEC_OK) {
+            g.signal_name = H(x.sp[0]);
+            g.input = H(x.sp[1]);
+            g.control = H(x.sp[2]);
+          }
+        }
+      }
+      if (P == COUNT) {
+        C.status[r] = err;
+        if (err != CDR_DEC_OK) atomicMin(&C.fail[w], fail_word(TBL, r - umin32(C.row0[w], r), err));
+      }
+      if (P == FILL) {
+        const uint32_t d = C.dest[r];
+        if (d < C.n_rows) {  // (unranked: a row outside its entry's range, malformed entry_row0)
+          typedef typename RecOf<TBL>::type Rec;
+          const uint64_t* s = reinterpret_cast<const uint64_t*>(&x.rec);
+          uint64_t* o = reinterpret_cast<uint64_t*>(reinterpret_cast<Rec*>(C.recs) + d);
+#pragma unroll
+          for (uint32_t i = 0; i < sizeof(Rec) / 8; i++) o[i] = s[i];
+        }
+      }
+    } else if (P == INTERN && TBL == 1) {
+      C.tkey[r] = 0;
+    }
+  }
+  if (P == COUNT) {  // the table's size: string fields, one atomic per wave
+    for (int o = 32; o > 0; o >>= 1) n_str += __shfl_down(n_str, o, 64);
+    if (lane == 0 && n_str) atomicAdd(C.totals, (unsigned long long)n_str);
+  }
+}
+
+// the entry of each row: the last w with entry_row0[w] <= r (empty entries share a start)
+__global__ void k_row_entry(const uint32_t* row0, uint32_t n_entries, uint32_t n_rows, uint32_t* row_entry) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n_rows) return;
+  uint32_t lo = 0, hi = n_entries - 1;
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo + 1) / 2;
+    if (row0[mid] <= r) lo = mid;
+    else hi = mid - 1;
+  }
+  row_entry[r] = lo;
+}
+
+// the generated run-ID texts into the string table, after every string of the rows
+__global__ void k_gen_intern(STab T, const uint8_t* gen, const uint32_t* row_entry, const unsigned long long* fail,
+                             uint32_t n_rows) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n_rows || fail[row_entry[r]] != NO_FAIL) return;
+  const uint8_t* g = gen + (uint64_t)GEN_BYTES * r;
+  if (g[0] == 0) return;
+  tab_insert(T, cdr_str_hash(g, GEN_BYTES), ((uint64_t)GEN_BYTES * r) | GEN_REF, GEN_BYTES, UNASSIGNED);
+}
+
+// timer keys: the ID's hash (INTERN) -> its handle
+__global__ void k_timer_keys(STab T, int64_t* tkey, uint32_t n_rows) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n_rows) return;
+  const uint64_t h = (uint64_t)tkey[r];
+  tkey[r] = h ? (int64_t)tab_lookup(T, h) : 0;
+}
+
+// RANK: the row's slot among its entry's rows by key; equal keys fail the entry, and so does
+// a table with more than CDR_LOAD_MAX_ENTRY_ROWS rows of the entry
+__global__ void k_rank_rows(const int64_t* key, const uint32_t* row_entry, const uint32_t* row0, uint32_t n_rows,
+                            uint32_t n_entries, unsigned long long* fail, int32_t* status, uint32_t* dest,
+                            uint32_t table) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n_rows) return;
+  const uint32_t w = row_entry[r];
+  if (fail[w] != NO_FAIL) return;
+  const uint32_t lo = umin32(row0[w], n_rows), hi = umin32(row0[w + 1], n_rows);
+  if (r < lo || r >= hi) return;
+  if (hi - lo > CDR_LOAD_MAX_ENTRY_ROWS) {  // every lane walks its entry's rows: bounded (cdr.h)
+    status[r] = CDR_LOAD_E_ENTRY_ROWS;
+    if (r == lo) atomicMin(&fail[n_entries + w], fail_word(table, 0, CDR_LOAD_E_ENTRY_ROWS));
+    return;
+  }
+  const int64_t k = key[r];
+  uint32_t below = 0, same = 0;
+  for (uint32_t j = lo; j < hi; j++) {
+    const int64_t kj = key[j];
+    below += kj < k ? 1u : 0u;
+    same += kj == k ? 1u : 0u;
+  }
+  dest[r] = lo + below;
+  if (same > 1) {
+    status[r] = CDR_LOAD_E_DUP_KEY;
+    atomicMin(&fail[n_entries + w], fail_word(table, r - lo, CDR_LOAD_E_DUP_KEY));
+  }
+}
+
+struct EpiIn {
+  const uint32_t* row0[CDR_LOAD_TABLES];
+  uint32_t n_rows[CDR_LOAD_TABLES];
+};
+__global__ void k_epilogue(EpiIn E, uint32_t n_entries, const unsigned long long* fail, cdr_wf_result* result,
+                           cdr_wf_caps* caps, int32_t* entry_status, uint32_t* n_bad) {
+  const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= n_entries) return;
+  unsigned long long f = fail[w];
+  if (f == NO_FAIL) f = fail[n_entries + w];
+  const bool ok = f == NO_FAIL;
+  uint64_t off[CDR_LOAD_TABLES];
+  uint32_t cnt[CDR_LOAD_TABLES];
+#pragma unroll
+  for (int t = 0; t < CDR_LOAD_TABLES; t++) {
+    const uint32_t a = E.row0[t] ? umin32(E.row0[t][w], E.n_rows[t]) : 0u;
+    const uint32_t b = E.row0[t] ? umin32(E.row0[t][w + 1], E.n_rows[t]) : 0u;
+    off[t] = a;
+    cnt[t] = b > a ? b - a : 0u;
+  }
+  cdr_wf_result res;
+  {
+    uint64_t* z = reinterpret_cast<uint64_t*>(&res);
+#pragma unroll
+    for (uint32_t i = 0; i < sizeof(res) / 8; i++) z[i] = 0;
+  }
+  res.code = ok ? CDR_OK : CDR_E_LOAD_ROWS;
+  res.n_activity = ok ? cnt[0] : 0u;
+  res.n_timer = ok ? cnt[1] : 0u;
+  res.n_child = ok ? cnt[2] : 0u;
+  res.n_cancel = ok ? cnt[3] : 0u;
+  res.n_signal = ok ? cnt[4] : 0u;
+  cdr_wf_caps c;
+  {
+    uint64_t* z = reinterpret_cast<uint64_t*>(&c);
+#pragma unroll
+    for (uint32_t i = 0; i < sizeof(c) / 8; i++) z[i] = 0;
+  }
+  c.act_off = off[0], c.timer_off = off[1], c.child_off = off[2], c.cancel_off = off[3], c.signal_off = off[4];
+  c.act_cap = cnt[0], c.timer_cap = cnt[1], c.child_cap = cnt[2], c.cancel_cap = cnt[3], c.signal_cap = cnt[4];
+  result[w] = res;
+  caps[w] = c;
+  entry_status[w] = ok ? CDR_DEC_OK : (int32_t)(f & 0xFFu);
+  if (!ok) atomicAdd(n_bad, 1u);
+}
+
+// ---------------------------------------------------------------- string table gather
+__global__ void k_gather_len(const uint32_t* str_len, uint32_t n, uint64_t* lens) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > n) return;
+  lens[i] = i < n ? str_len[i] : 0u;
+}
+// one wavefront per string
+__global__ __launch_bounds__(256) void k_gather_copy(const uint64_t* str_ref, const uint32_t* str_len, uint32_t n,
+                                                     const uint8_t* bytes, const uint8_t* seed_bytes,
+                                                     const uint8_t* gen_bytes, const uint64_t* off, uint8_t* out) {
+  const uint32_t h = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  if (h >= n) return;
+  const uint64_t ref = str_ref[h];
+  const uint8_t* src = (ref & SEED_REF) ? seed_bytes : (ref & GEN_REF) ? gen_bytes : bytes;
+  if (!src) return;
+  src += ref & ~(SEED_REF | GEN_REF);
+  uint8_t* dst = out + off[h];
+  const uint32_t len = str_len[h];
+  for (uint32_t i = lane; i < len; i += 64) dst[i] = src[i];
+}
+
+template <class T>
+int ws(cdr_ctx* c, int slot, uint64_t n, T** p) {
+  *p = (T*)cdr_ws_get(c, slot, n * sizeof(T) + 8);
+  return *p ? CDR_API_OK : CDR_API_ENOMEM;
+}
+
+template <int P>
+void launch_rows(int t, const LCtx& C, hipStream_t st) {
+  if (!C.n_rows) return;
+  const dim3 grid((C.n_rows + CDR_LOAD_BLOCK - 1) / CDR_LOAD_BLOCK), blk(CDR_LOAD_BLOCK);
+  const size_t lds = (CDR_LOAD_BLOCK / 64) * CDR_LOAD_STAGE;
+  switch (t) {
+    case 0: hipLaunchKernelGGL((k_rows<0, P>), grid, blk, lds, st, C); break;
+    case 1: hipLaunchKernelGGL((k_rows<1, P>), grid, blk, lds, st, C); break;
+    case 2: hipLaunchKernelGGL((k_rows<2, P>), grid, blk, lds, st, C); break;
+    case 3: hipLaunchKernelGGL((k_rows<3, P>), grid, blk, lds, st, C); break;
+    default: hipLaunchKernelGGL((k_rows<4, P>), grid, blk, lds, st, C); break;
+  }
+}
+
+}  // namespace
+
+extern "C" int cdr_load_rows(cdr_ctx* ctx, const cdr_rows_in* in, cdr_rows_out* out, void* stream) {
+  if (!ctx || !in || !out || !in->seed_off || in->n_seeds == 0) return CDR_API_EINVAL;
+  constexpr int NT = CDR_LOAD_TABLES;
+  uint64_t n_all = 0, base[NT + 1];
+  for (int t = 0; t < NT; t++) {
+    base[t] = n_all;
+    n_all += in->n_rows[t];
+    if (!in->n_rows[t]) continue;
+    if (!in->blob_off[t] || !in->entry_row0[t] || (t != 1 && !in->key[t])) return CDR_API_EINVAL;
+  }
+  base[NT] = n_all;
+  if ((in->n_rows[1] && !in->timer_id_off) || (in->n_rows[0] && !in->act_heartbeat)) return CDR_API_EINVAL;
+  if (n_all && (!in->n_entries || (in->n_bytes && !in->bytes))) return CDR_API_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(hipSetDevice(cdr_ctx_device(ctx)));
+  const uint32_t ne = in->n_entries;
+  *out = cdr_rows_out{};
+  // every row belongs to an entry: entry_row0 runs from 0 to n_rows
+  {
+    uint32_t ends[NT][2] = {};
+    for (int t = 0; t < NT; t++) {
+      if (!in->n_rows[t]) continue;
+      HIPCHK(hipMemcpyAsync(&ends[t][0], in->entry_row0[t], 4, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(&ends[t][1], in->entry_row0[t] + ne, 4, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    for (int t = 0; t < NT; t++)
+      if (in->n_rows[t] && (ends[t][0] != 0 || ends[t][1] != in->n_rows[t])) return CDR_API_EINVAL;
+  }
+  for (hipEvent_t& e : ctx->ld_ev)
+    if (!e) HIPCHK(hipEventCreate(&e));
+  HIPCHK(hipEventRecord(ctx->ld_ev[0], st));
+  int rc;
+  uint32_t *row_entry, *dest, *misc;
+  int32_t *status, *estatus;
+  int64_t* tkey;
+  unsigned long long* fail;
+  cdr_wf_result* result;
+  cdr_wf_caps* caps;
+  uint8_t* gen;
+  void* recs[NT];
+  static const int rec_slot[NT] = {WS_LD_ACT, WS_LD_TIMER, WS_LD_CHILD, WS_LD_CANCEL, WS_LD_SIGNAL};
+  static const uint64_t rec_size[NT] = {sizeof(cdr_activity_info), sizeof(cdr_timer_info), sizeof(cdr_child_info),
+                                        sizeof(cdr_cancel_info), sizeof(cdr_signal_info)};
+  if ((rc = ws(ctx, WS_LD_ROWENT, n_all + 1, &row_entry)) || (rc = ws(ctx, WS_LD_STATUS, n_all + 1, &status)) ||
+      (rc = ws(ctx, WS_LD_DEST, n_all + 1, &dest)) || (rc = ws(ctx, WS_LD_TKEY, in->n_rows[1] + 1ull, &tkey)) ||
+      (rc = ws(ctx, WS_LD_FAIL, 2ull * ne + 1, &fail)) || (rc = ws(ctx, WS_LD_ESTATUS, ne + 1ull, &estatus)) ||
+      (rc = ws(ctx, WS_LD_RESULT, ne + 1ull, &result)) || (rc = ws(ctx, WS_LD_CAPS, ne + 1ull, &caps)) ||
+      (rc = ws(ctx, WS_LD_GEN, (uint64_t)GEN_BYTES * in->n_rows[2] + 8, &gen)) ||
+      (rc = ws(ctx, WS_LD_MISC, 16, &misc)))
+    return rc;
+  for (int t = 0; t < NT; t++) {
+    recs[t] = cdr_ws_get(ctx, rec_slot[t], (in->n_rows[t] + 1ull) * rec_size[t]);
+    if (!recs[t]) return CDR_API_ENOMEM;
+  }
+  const dim3 blk(256);
+  auto grid = [](uint64_t n) { return dim3((uint32_t)((n + 255) / 256)); };
+  // misc, as u32 words: [0] table overflow, [1] new strings, [2] failed entries, [3] unused,
+  // [4..5] one u64: string fields
+  unsigned long long* n_fields = reinterpret_cast<unsigned long long*>(misc) + 2;
+  HIPCHK(hipMemsetAsync(misc, 0, 64, st));
+  HIPCHK(hipMemsetAsync(fail, 0xFF, (2ull * ne + 1) * 8, st));
+  HIPCHK(hipMemsetAsync(dest, 0xFF, (n_all + 1) * 4, st));
+  LCtx C[NT];
+  for (int t = 0; t < NT; t++) {
+    LCtx& c = C[t];
+    c = LCtx{};
+    c.bytes = in->bytes;
+    c.total = in->n_bytes;
+    c.blob_off = in->blob_off[t];
+    c.tid_off = in->timer_id_off;
+    c.key = in->key[t];
+    c.hb = in->act_heartbeat;
+    c.row_entry = row_entry + base[t];
+    c.row0 = in->entry_row0[t];
+    c.fail = fail;
+    c.status = status + base[t];
+    c.totals = n_fields;
+    c.gen = gen;
+    c.dest = dest + base[t];
+    c.recs = recs[t];
+    c.tkey = tkey;
+    c.n_rows = in->n_rows[t];
+    c.n_entries = ne;
+    if (c.n_rows)
+      hipLaunchKernelGGL(k_row_entry, grid(c.n_rows), blk, 0, st, c.row0, ne, c.n_rows, row_entry + base[t]);
+  }
+  HIPCHK(hipGetLastError());
+  // ---- pass 1: statuses and string-field counts
+  for (int t = 0; t < NT; t++) launch_rows<COUNT>(t, C[t], st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(ctx->ld_ev[1], st));
+  uint64_t n_str_fields = 0;
+  HIPCHK(hipMemcpyAsync(&n_str_fields, n_fields, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  uint64_t cap = 1024;
+  while (cap < 2 * (n_str_fields + in->n_seeds)) cap <<= 1;
+  STab T{};
+  T.mask = cap - 1;
+  if ((rc = ws(ctx, WS_LD_TABKEY, cap, (unsigned long long**)&T.key)) || (rc = ws(ctx, WS_LD_TABVAL, cap, &T.val)) ||
+      (rc = ws(ctx, WS_LD_TABREF, cap, &T.ref)) || (rc = ws(ctx, WS_LD_TABLEN, cap, &T.len)))
+    return rc;
+  T.overflow = misc;
+  HIPCHK(hipMemsetAsync(T.key, 0, cap * 8, st));
+  // ---- pass 2: seeds, the rows' strings, the generated run IDs; rank the new ones by hash
+  hipLaunchKernelGGL(k_seed, grid(in->n_seeds), blk, 0, st, T, in->seed_bytes, in->seed_off, in->n_seeds);
+  for (int t = 0; t < NT; t++) {
+    C[t].T = T;
+    launch_rows<INTERN>(t, C[t], st);
+  }
+  if (in->n_rows[2])
+    hipLaunchKernelGGL(k_gen_intern, grid(in->n_rows[2]), blk, 0, st, T, gen, row_entry + base[2], fail,
+                       in->n_rows[2]);
+  HIPCHK(hipGetLastError());
+  unsigned long long *k1, *k2;
+  uint64_t *i1, *i2;
+  uint32_t *ccount, *coffs;
+  if ((rc = ws(ctx, WS_LD_SKEY, n_str_fields + 1, &k1)) || (rc = ws(ctx, WS_LD_SKEY2, n_str_fields + 1, &k2)) ||
+      (rc = ws(ctx, WS_LD_SIDX, n_str_fields + 1, &i1)) || (rc = ws(ctx, WS_LD_SIDX2, n_str_fields + 1, &i2)) ||
+      (rc = ws(ctx, WS_LD_STRREF, n_str_fields + in->n_seeds + 1, &out->str_ref)) ||
+      (rc = ws(ctx, WS_LD_STRLEN, n_str_fields + in->n_seeds + 1, &out->str_len)) ||
+      (rc = ws(ctx, WS_LD_CCOUNT, COLLECT_WG + 1ull, &ccount)) || (rc = ws(ctx, WS_LD_COFFS, COLLECT_WG + 1ull, &coffs)))
+    return rc;
+  {
+    HIPCHK(hipMemsetAsync(ccount + COLLECT_WG, 0, 4, st));
+    hipLaunchKernelGGL(k_collect_count, dim3(COLLECT_WG), blk, 0, st, T, ccount);
+    size_t tb = 0;
+    HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, ccount, coffs, (int)(COLLECT_WG + 1), st));
+    void* tmp = cdr_ws_get(ctx, WS_LD_CTMP, tb ? tb : 8);
+    if (!tmp) return CDR_API_ENOMEM;
+    HIPCHK(hipcub::DeviceScan::ExclusiveSum(tmp, tb, ccount, coffs, (int)(COLLECT_WG + 1), st));
+    hipLaunchKernelGGL(k_collect_write, dim3(COLLECT_WG), blk, 0, st, T, coffs, k1, i1);
+    HIPCHK(hipMemcpyAsync(misc + 1, coffs + COLLECT_WG, 4, hipMemcpyDeviceToDevice, st));
+  }
+  HIPCHK(hipGetLastError());
+  uint32_t hm[2];
+  HIPCHK(hipMemcpyAsync(hm, misc, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (hm[0]) return CDR_API_ENOMEM;  // table overflow: cannot happen at twice the fields
+  const uint32_t n_new = hm[1];
+  if (n_new) {
+    hipcub::DoubleBuffer<unsigned long long> kb(k1, k2);
+    hipcub::DoubleBuffer<uint64_t> vb(i1, i2);
+    size_t tmp_bytes = 0;
+    HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, kb, vb, (int)n_new, 0, 64, st));
+    void* sort_tmp = cdr_ws_get(ctx, WS_LD_SORTTMP, tmp_bytes ? tmp_bytes : 8);
+    if (!sort_tmp) return CDR_API_ENOMEM;
+    HIPCHK(hipcub::DeviceRadixSort::SortPairs(sort_tmp, tmp_bytes, kb, vb, (int)n_new, 0, 64, st));
+    hipLaunchKernelGGL(k_rank, grid(n_new), blk, 0, st, T, vb.Current(), n_new, in->n_seeds, out->str_ref,
+                       out->str_len);
+  }
+  hipLaunchKernelGGL(k_seed_refs, grid(in->n_seeds), blk, 0, st, in->seed_off, in->n_seeds, out->str_ref,
+                     out->str_len);
+  HIPCHK(hipGetLastError());
+  out->n_strings = in->n_seeds + n_new;
+  HIPCHK(hipEventRecord(ctx->ld_ev[2], st));
+  // ---- pass 3: each row's slot in key order (timer keys: the handles, known now)
+  if (in->n_rows[1]) hipLaunchKernelGGL(k_timer_keys, grid(in->n_rows[1]), blk, 0, st, T, tkey, in->n_rows[1]);
+  for (int t = 0; t < NT; t++)
+    if (in->n_rows[t])
+      hipLaunchKernelGGL(k_rank_rows, grid(in->n_rows[t]), blk, 0, st, t == 1 ? (const int64_t*)tkey : in->key[t],
+                         row_entry + base[t], in->entry_row0[t], in->n_rows[t], ne, fail, status + base[t],
+                         dest + base[t], (uint32_t)t);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(ctx->ld_ev[3], st));
+  // ---- pass 4: the records, then the entries
+  for (int t = 0; t < NT; t++) launch_rows<FILL>(t, C[t], st);
+  EpiIn E{};
+  for (int t = 0; t < NT; t++) {
+    E.row0[t] = in->entry_row0[t];
+    E.n_rows[t] = in->n_rows[t];
+  }
+  if (ne) hipLaunchKernelGGL(k_epilogue, grid(ne), blk, 0, st, E, ne, fail, result, caps, estatus, misc + 2);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(ctx->ld_ev[4], st));
+  uint32_t n_bad = 0;
+  HIPCHK(hipMemcpyAsync(&n_bad, misc + 2, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (int i = 0; i < 4; i++) HIPCHK(hipEventElapsedTime(&ctx->ld_ms[i], ctx->ld_ev[i], ctx->ld_ev[i + 1]));
+  out->state.result = result;
+  out->state.act = (cdr_activity_info*)recs[0];
+  out->state.timer = (cdr_timer_info*)recs[1];
+  out->state.child = (cdr_child_info*)recs[2];
+  out->state.cancel = (cdr_cancel_info*)recs[3];
+  out->state.signal = (cdr_signal_info*)recs[4];
+  out->caps = caps;
+  out->totals.act = in->n_rows[0];
+  out->totals.timer = in->n_rows[1];
+  out->totals.child = in->n_rows[2];
+  out->totals.cancel = in->n_rows[3];
+  out->totals.signal = in->n_rows[4];
+  for (int t = 0; t < NT; t++) out->row_status[t] = status + base[t];
+  out->entry_status = estatus;
+  out->gen_bytes = gen;
+  out->n_gen_bytes = (uint64_t)GEN_BYTES * in->n_rows[2];
+  out->n_bad_entries = n_bad;
+  return CDR_API_OK;
+}
+
+extern "C" int cdr_load_pass_ms(cdr_ctx* ctx, float* ms) {
+  if (!ctx || !ms) return CDR_API_EINVAL;
+  for (int i = 0; i < 4; i++) ms[i] = ctx->ld_ms[i];
+  return CDR_API_OK;
+}
+
+extern "C" int cdr_strtab_gather_async(cdr_ctx* ctx, const uint64_t* str_ref, const uint32_t* str_len, uint32_t n,
+                                       const uint8_t* bytes, const uint8_t* seed_bytes, const uint8_t* gen_bytes,
+                                       uint64_t* off, uint8_t* out_bytes, void* stream) {
+  if (!ctx || !off || (n && (!str_ref || !str_len))) return CDR_API_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(hipSetDevice(cdr_ctx_device(ctx)));
+  if (!out_bytes) {  // sizes: off[0 .. n] = exclusive scan of the lengths
+    size_t tb = 0;
+    HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, (uint64_t*)nullptr, off, (int)(n + 1), st));
+    const uint64_t lens_bytes = ((n + 1ull) * 8 + 255) & ~255ull;
+    uint8_t* tmp = (uint8_t*)cdr_ws_get(ctx, WS_GATHER_TMP, lens_bytes + (tb ? tb : 8));
+    if (!tmp) return CDR_API_ENOMEM;
+    uint64_t* lens = (uint64_t*)tmp;
+    hipLaunchKernelGGL(k_gather_len, dim3((n + 256) / 256), dim3(256), 0, st, str_len, n, lens);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipcub::DeviceScan::ExclusiveSum(tmp + lens_bytes, tb, lens, off, (int)(n + 1), st));
+    return CDR_API_OK;
+  }
+  if (n)
+    hipLaunchKernelGGL(k_gather_copy, dim3((n + 3) / 4), dim3(256), 0, st, str_ref, str_len, n, bytes, seed_bytes,
+                       gen_bytes, off, out_bytes);
+  HIPCHK(hipGetLastError());
+  return CDR_API_OK;
+}

@@ -2242,6 +2242,8 @@ void cdr_destroy(cdr_ctx* c) {
     if (c->join[i]) (void)hipEventDestroy(c->join[i]);
   }
   if (c->fork) (void)hipEventDestroy(c->fork);
+  for (hipEvent_t e : c->ld_ev)
+    if (e) (void)hipEventDestroy(e);
   if (hipSetDevice(c->device) == hipSuccess)
     for (void* p : c->ws) (void)hipFree(p);
   for (void* p : c->hs)

@@ -24,11 +24,15 @@ def stand_in(h: int, strings=None) -> bytes:
     return b"h%08x" % h
 
 
-def _table(strings):
+def string_table(strings):
+    """(bytes, offsets [n + 1]) of a list of strings: the host form of a cdr_strtab / the seeds."""
     bs = [s.encode() if isinstance(s, str) else bytes(s) for s in strings]
     off = np.zeros(len(bs) + 1, np.uint64)
     off[1:] = np.cumsum([len(b) for b in bs]) if bs else []
     return np.frombuffer(b"".join(bs) or b"\0", np.uint8).copy(), off
+
+
+_table = string_table
 
 
 @dataclasses.dataclass

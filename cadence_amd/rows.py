@@ -1,0 +1,340 @@
+"""Host side of the persisted-row loader (cdr.h cdr_load_rows, csrc/load.hip).
+
+``encode_state`` runs the existing row encoders over the five pending tables of replayed
+states and packs their blobs the way a store would hand them back (a ``Rows``, the host
+form of cdr_rows_in); ``load`` decodes a ``Rows`` on the device and returns host copies
+of every output; ``to_carry`` turns a decode plus the caller's exec / repl / vh / rp / sa
+records (the execution row is not decoded: cdr.h) into an ``engine.Carry`` a batch can
+replay onto.  ``gather`` runs cdr_strtab_gather_async on any decoded string table.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import dataclasses
+import struct
+from types import SimpleNamespace
+
+import numpy as np
+
+from . import abi, engine
+from .ingest import stand_in, string_table
+
+TABLES = ("act", "timer", "child", "cancel", "signal")  # cdr.h table numbers 0 .. 4
+KEY = {"act": "schedule_id", "child": "initiated_id", "cancel": "initiated_id", "signal": "initiated_id"}
+HANDLES = {"act": ("activity_id", "request_id", "task_list", "nonretriable"), "timer": ("timer_id",),
+           "child": ("started_workflow_id", "started_run_id", "domain_name", "workflow_type"), "cancel": (),
+           "signal": ("signal_name", "input", "control")}
+
+
+@dataclasses.dataclass
+class Rows:
+    """cdr_rows_in on the host.  Row r of table t: blob bytes[blob_off[t][r]:blob_off[t][r+1]],
+    key[t][r] (tables 0, 2-4) or the timer ID bytes[timer_id_off[r]:timer_id_off[r+1]]
+    (table 1); entry w owns rows [entry_row0[t][w], entry_row0[t][w+1])."""
+    bytes: np.ndarray          # uint8
+    blob_off: list             # 5 x uint64 [n_rows + 1]
+    entry_row0: list           # 5 x uint32 [n_entries + 1]
+    key: list                  # 5 x int64 [n_rows] (key[1] is empty)
+    timer_id_off: np.ndarray   # uint64 [n_rows[1] + 1]
+    act_heartbeat: np.ndarray  # int64 [n_rows[0]]
+    n_entries: int
+    src: list = None           # encode_state: 5 x [(entry, row j of the entry)] per packed row
+
+    @property
+    def n_rows(self):
+        return [len(o) - 1 for o in self.blob_off]
+
+    def blob(self, t: int, r: int) -> bytes:
+        return self.bytes[int(self.blob_off[t][r]):int(self.blob_off[t][r + 1])].tobytes()
+
+    def timer_id(self, r: int) -> bytes:
+        return self.bytes[int(self.timer_id_off[r]):int(self.timer_id_off[r + 1])].tobytes()
+
+
+def pack(n_entries: int, tables) -> Rows:
+    """tables[t][w] = entry w's rows of table t in arrival order: (key, blob) for tables 0,
+    2, 3, 4 — table 0 may add a third item, the heartbeat column (default: Go's zero time) —
+    and (timer ID bytes, blob) for table 1.  Each table's blobs are contiguous in `bytes`,
+    the timer IDs follow the last blob."""
+    chunks, pos = [], 0
+    offs, row0, keys, hb, ids = [], [], [], [], []
+    for t in range(5):
+        off, r0, ks = [pos], [0], []
+        for w in range(n_entries):
+            for row in tables[t][w]:
+                if t == 1:
+                    ids.append(bytes(row[0]))
+                else:
+                    ks.append(row[0])
+                    if t == 0:
+                        hb.append(row[2] if len(row) > 2 else abi.ZERO_TIME_NANOS)
+                chunks.append(bytes(row[1]))
+                pos += len(row[1])
+                off.append(pos)
+            r0.append(len(off) - 1)
+        offs.append(np.array(off, np.uint64))
+        row0.append(np.array(r0, np.uint32))
+        keys.append(np.array(ks, np.int64))
+    tid_off = [pos]
+    for s in ids:
+        chunks.append(s)
+        pos += len(s)
+        tid_off.append(pos)
+    data = np.frombuffer(b"".join(chunks) or b"\0", np.uint8).copy()
+    return Rows(data[:pos], offs, row0, keys, np.array(tid_off, np.uint64), np.array(hb, np.int64), n_entries)
+
+
+def heartbeat_column(a) -> int:
+    """The LastHeartbeatUpdatedTime column of an activity record: its heartbeat time when
+    either time bit says it is a real instant, else Go's zero time."""
+    if a.flags & (abi.AI_STARTED_TIME_SET | abi.AI_HEARTBEAT_TIME_SET):
+        return a.last_heartbeat_time
+    return abi.ZERO_TIME_NANOS
+
+
+def run_id_text(h: int) -> bytes:
+    return b"%08x-0000-4000-8000-%012x" % (h & 0xFFFFFFFF, h)
+
+
+def state_strings(batch: engine.Batch, out: engine.Outputs, strings=None) -> list:
+    """A table of distinct strings covering every handle the pending tables of `out` name:
+    ingest.stand_in's string per handle (or `strings`), canonical UUID text for the handles
+    used as a child's started run ID, a one-element list<string> body for the handles used
+    as RetryNonRetryableErrors."""
+    hmax, runs, lists = 1, set(), set()
+    for w in range(batch.n_wfs):
+        if out.result[w].code != abi.OK:
+            continue
+        for t in TABLES:
+            for r in out.rows(w, t):
+                hmax = max([hmax] + [getattr(r, f) for f in HANDLES[t]])
+                if t == "child" and r.started_run_id:
+                    runs.add(r.started_run_id)
+                if t == "act" and r.nonretriable:
+                    lists.add(r.nonretriable)
+    tab = [b""] + [stand_in(h, strings) for h in range(1, hmax + 1)]
+    for h in runs:
+        tab[h] = run_id_text(h)
+    for h in lists - runs:
+        s = stand_in(h, strings)
+        tab[h] = struct.pack(">bi", 11, 1) + struct.pack(">i", len(s)) + s
+    return tab
+
+
+def encode_state(eng: engine.Engine, batch: engine.Batch, out: engine.Outputs, strings: list) -> Rows:
+    """The five pending tables of the OK entries of `out` as the SQL persistence stores
+    them: the device encoders' blobs (cdr_encode_blobs_async / cdr_encode_rows_async), the
+    key columns and the activity heartbeat column from the records, timer IDs from
+    `strings`.  A row an encoder refuses (status != 0) is left out of its entry.
+    `.src[t]` names each packed row's (entry, row of the entry)."""
+    blobs = {}
+    for t in TABLES:
+        if t in ("timer", "cancel"):
+            blobs[t] = eng.encode_rows(batch, out, t)
+        else:
+            got, codes = eng.encode_blobs(batch, out, t, strings)
+            blobs[t] = {r: b for r, b in got.items() if codes[r] == 0}
+    tables, src = [], []
+    for t in TABLES:
+        per_entry, s = [], []
+        for w in range(batch.n_wfs):
+            rows = []
+            if out.result[w].code == abi.OK:
+                base = getattr(out.plan.caps[w], t + "_off")
+                for j, rec in enumerate(out.rows(w, t)):
+                    if base + j not in blobs[t]:
+                        continue
+                    if t == "timer":
+                        if rec.timer_id >= len(strings):
+                            continue
+                        rows.append((strings[rec.timer_id], blobs[t][base + j]))
+                    elif t == "act":
+                        rows.append((rec.schedule_id, blobs[t][base + j], heartbeat_column(rec)))
+                    else:
+                        rows.append((getattr(rec, KEY[t]), blobs[t][base + j]))
+                    s.append((w, j))
+            per_entry.append(rows)
+        tables.append(per_entry)
+        src.append(s)
+    rows = pack(batch.n_wfs, tables)
+    rows.src = src
+    return rows
+
+
+@dataclasses.dataclass
+class Loaded:
+    tables: dict              # "act" .. "signal" -> ctypes record arrays [n_rows[t]]
+    result: C.Array           # cdr_wf_result [n_entries]
+    caps: C.Array             # cdr_wf_caps [n_entries]
+    totals: abi.CdrTotals
+    row_status: list          # 5 x int32 [n_rows[t]]
+    entry_status: np.ndarray  # int32 [n_entries]
+    strings: list             # bytes per handle
+    str_ref: np.ndarray
+    str_len: np.ndarray
+    gen_bytes: bytes
+    n_bad_entries: int
+    gathered: list = None     # load(gather=True): the table cdr_strtab_gather_async built
+    rc: int = 0
+
+    def rows(self, w: int, t: str):
+        off = getattr(self.caps[w], t + "_off")
+        return [self.tables[t][off + j] for j in range(getattr(self.result[w], engine.TABLE_COUNT[t]))]
+
+
+class DeviceBuffers:
+    """Device buffers of one call, freed together."""
+
+    def __init__(self):
+        self.hip, self.ptrs = engine._hip(), []
+
+    def alloc(self, nbytes: int) -> int:
+        p = C.c_void_p()
+        if self.hip.hipMalloc(C.byref(p), C.c_size_t(max(8, nbytes))) != 0:
+            raise RuntimeError("hipMalloc failed")
+        self.ptrs.append(p)
+        return p.value
+
+    def up(self, a: np.ndarray, at_end: bool = False) -> int:
+        a = np.ascontiguousarray(a)
+        if at_end:  # the array's last byte is the last byte of its allocation
+            size = (a.nbytes + 4095) // 4096 * 4096 or 4096
+            p = self.alloc(size) + size - a.nbytes
+        else:
+            p = self.alloc(a.nbytes)
+        if a.nbytes and self.hip.hipMemcpy(C.c_void_p(p), a.ctypes.data, C.c_size_t(a.nbytes), 1) != 0:
+            raise RuntimeError("hipMemcpy H2D failed")
+        return p
+
+    def down(self, ptr, dtype, n: int) -> np.ndarray:
+        out = np.zeros(max(1, n), dtype)
+        if n and self.hip.hipMemcpy(out.ctypes.data, C.c_void_p(ptr), C.c_size_t(n * out.itemsize), 2) != 0:
+            raise RuntimeError("hipMemcpy D2H failed")
+        return out[:n]
+
+    def free(self):
+        for p in self.ptrs:
+            self.hip.hipFree(p)
+        self.ptrs = []
+
+
+def _gather(eng, dev: DeviceBuffers, str_ref, str_len, n: int, d_bytes, d_seeds, d_gen) -> list:
+    L = abi.lib()
+    off = dev.alloc(8 * (n + 1))
+    rc = L.cdr_strtab_gather_async(eng.ctx, str_ref, str_len, n, d_bytes, d_seeds, d_gen, off, None, None)
+    if rc:
+        raise RuntimeError(f"cdr_strtab_gather_async (sizes) rc={rc}")
+    offs = dev.down(off, np.uint64, n + 1)
+    total = int(offs[-1]) if n else 0
+    buf = dev.alloc(total)
+    rc = L.cdr_strtab_gather_async(eng.ctx, str_ref, str_len, n, d_bytes, d_seeds, d_gen, off, buf, None)
+    if rc:
+        raise RuntimeError(f"cdr_strtab_gather_async (copy) rc={rc}")
+    raw = dev.down(buf, np.uint8, total).tobytes()
+    return [raw[int(offs[h]):int(offs[h + 1])] for h in range(n)]
+
+
+def gather(eng: engine.Engine, str_ref: int, str_len: int, n: int, blob_bytes: np.ndarray, seeds: list) -> list:
+    """cdr_strtab_gather_async on a decoded table still resident in the context (device
+    pointers str_ref / str_len, e.g. a cdr_ingest_out's; gen_bytes NULL): bytes per handle."""
+    dev = DeviceBuffers()
+    try:
+        sb, _ = string_table(seeds)
+        return _gather(eng, dev, str_ref, str_len, n, dev.up(blob_bytes), dev.up(sb), None)
+    finally:
+        dev.free()
+
+
+def load(eng: engine.Engine, rows: Rows, seeds: list, at_end: bool = False, gather: bool = False,
+         check: bool = True) -> Loaded:
+    """cdr_load_rows on the device; host copies of every output.  `at_end`: `bytes` is
+    uploaded so that it ends where its allocation ends.  `gather`: also build the
+    contiguous string table on the device (cdr_strtab_gather_async) -> .gathered.
+    check=False returns the call's status in .rc instead of raising."""
+    L = abi.lib()
+    dev = DeviceBuffers()
+    try:
+        sb, so = string_table(seeds)
+        inp = abi.CdrRowsIn()
+        inp.bytes = dev.up(rows.bytes if len(rows.bytes) else np.zeros(1, np.uint8), at_end and len(rows.bytes) > 0)
+        inp.n_bytes = len(rows.bytes)
+        n_rows = rows.n_rows
+        for t in range(5):
+            inp.blob_off[t] = dev.up(rows.blob_off[t])
+            inp.entry_row0[t] = dev.up(rows.entry_row0[t])
+            inp.key[t] = dev.up(rows.key[t]) if t != 1 else None
+            inp.n_rows[t] = n_rows[t]
+        inp.timer_id_off = dev.up(rows.timer_id_off)
+        inp.act_heartbeat = dev.up(rows.act_heartbeat)
+        inp.seed_bytes, inp.seed_off = dev.up(sb), dev.up(so)
+        inp.n_entries, inp.n_seeds = rows.n_entries, len(seeds)
+        out = abi.CdrRowsOut()
+        rc = L.cdr_load_rows(eng.ctx, C.byref(inp), C.byref(out), None)
+        if rc:
+            if check:
+                raise RuntimeError(f"cdr_load_rows rc={rc}")
+            return Loaded({}, None, None, abi.CdrTotals(), [], np.zeros(0, np.int32), [], None, None, b"", 0, rc=rc)
+        ne = rows.n_entries
+
+        def recs(ptr, ty, n):
+            raw = dev.down(ptr, np.uint8, n * C.sizeof(ty)).tobytes()
+            return (ty * n).from_buffer_copy(raw) if n else (ty * 0)()
+        tables = {t: recs(getattr(out.state, t), engine.TABLE_TYPES[t], n_rows[i]) for i, t in enumerate(TABLES)}
+        result = recs(out.state.result, abi.CdrWfResult, ne)
+        caps = recs(out.caps, abi.CdrWfCaps, ne)
+        status = [dev.down(out.row_status[t], np.int32, n_rows[t]) for t in range(5)]
+        est = dev.down(out.entry_status, np.int32, ne)
+        ref = dev.down(out.str_ref, np.uint64, out.n_strings)
+        ln = dev.down(out.str_len, np.uint32, out.n_strings)
+        gen = dev.down(out.gen_bytes, np.uint8, out.n_gen_bytes).tobytes()
+        raw, sraw = rows.bytes.tobytes(), sb.tobytes()
+        strings = []
+        for h in range(out.n_strings):
+            r, n = int(ref[h]), int(ln[h])
+            src = sraw if r & abi.STR_REF_SEED else gen if r & abi.STR_REF_GEN else raw
+            r &= abi.STR_REF_GEN - 1
+            strings.append(src[r:r + n])
+        res = Loaded(tables, result, caps, out.totals, status, est, strings, ref, ln, gen, out.n_bad_entries)
+        if gather:
+            res.gathered = _gather(eng, dev, out.str_ref, out.str_len, out.n_strings, inp.bytes, inp.seed_bytes,
+                                   out.gen_bytes)
+        return res
+    finally:
+        dev.free()
+
+
+def to_carry(loaded: Loaded, other: engine.Outputs, src=None) -> engine.Carry:
+    """A Carry over the decoded pending tables plus the caller's exec / repl / vh / rp / sa
+    records (`other`, entry for entry: the execution row is not decoded).  src defaults to
+    every entry that loaded and whose `other` record is OK (-1: fresh builder)."""
+    n = len(loaded.result)
+    assert n == other.n_wfs
+    caps = (abi.CdrWfCaps * max(1, n))()
+    tot = abi.CdrTotals()
+    for t in TABLES:
+        setattr(tot, t, getattr(loaded.totals, t))
+    for t in ("vh", "rp", "sa"):
+        setattr(tot, t, getattr(other.plan.totals, t))
+    st = engine.Outputs(SimpleNamespace(n_wfs=n), engine.Plan(caps, tot))
+    for w in range(n):
+        for t in TABLES:
+            setattr(caps[w], t + "_off", getattr(loaded.caps[w], t + "_off"))
+            setattr(caps[w], t + "_cap", getattr(loaded.caps[w], t + "_cap"))
+        for t in ("vh", "rp", "sa"):
+            setattr(caps[w], t + "_off", getattr(other.plan.caps[w], t + "_off"))
+            setattr(caps[w], t + "_cap", getattr(other.plan.caps[w], t + "_cap"))
+        r, lo, oo = st.result[w], loaded.result[w], other.result[w]
+        C.memmove(C.addressof(r), C.addressof(oo), C.sizeof(r))
+        if lo.code != abi.OK and oo.code == abi.OK:
+            r.code = lo.code
+        for t in TABLES:
+            setattr(r, engine.TABLE_COUNT[t], getattr(lo, engine.TABLE_COUNT[t]) if r.code == abi.OK else 0)
+    C.memmove(st.exec, other.exec, C.sizeof(abi.CdrExecInfo) * n)
+    C.memmove(st.repl, other.repl, C.sizeof(abi.CdrReplState) * n)
+    for t in TABLES:
+        C.memmove(st.tables[t], loaded.tables[t], C.sizeof(loaded.tables[t]))
+    for t in ("vh", "rp", "sa"):
+        C.memmove(st.tables[t], other.tables[t], C.sizeof(engine.TABLE_TYPES[t]) * getattr(tot, t))
+    if src is None:
+        src = np.array([w if st.result[w].code == abi.OK else -1 for w in range(n)], np.int32)
+    return engine.Carry(src=np.asarray(src, np.int32), state=st)

@@ -853,6 +853,147 @@ int cdr_ndc_replicate_async(cdr_ctx* ctx, uint32_t n, const cdr_ndc_round* round
  * loaded state has at most state_caps[w] rows; every entry replays in the general kernel). */
 int cdr_plan_ndc_apply(const cdr_batch* b, const cdr_wf_caps* state_caps, cdr_wf_caps* caps, cdr_totals* totals);
 
+/* ------------------------------------------- loading persisted rows (load.hip) */
+/* The inverse of the row encoders above for the SQL form: the five pending tables' row
+ * blobs decoded on the device, straight into the loaded-state tables cdr_carry takes — what
+ * mutableStateBuilder.Load (mutableStateBuilder.go:272-295) is fed by GetWorkflowExecution's
+ * getActivityInfoMap, getTimerInfoMap, getChildExecutionInfoMap, getRequestCancelInfoMap and
+ * getSignalInfoMap (common/persistence/sql/workflowStateMaps.go:139-206, 297-332, 423-471,
+ * 561-596, 689-727), all through thriftRWDecode (blob.go:75-84).  Tables are numbered as in
+ * the encoders: 0 activity, 1 timer, 2 child, 3 request-cancel, 4 signal.
+ * OUT OF SCOPE: the execution row (one per workflow, nested blobs, key columns whose UUIDs
+ * would need new text) — the caller keeps supplying the exec / repl / vh / rp / sa records —
+ * and the Cassandra form.
+ *
+ * Blob format.  A blob is a bare thriftrw binary-protocol struct with no 0x59 preamble
+ * (blob.go:61-84).  The wire rules are those of cdr/ingest.h: fields in any order, unknown
+ * fields skipped, a field of an unexpected wire type skipped (an earlier occurrence stays), a
+ * repeated field keeps its last occurrence, CDR_THRIFT_MAX_DEPTH bounds the containers open at
+ * once inside a skipped value (a kept list<string> included).  Bytes after the struct's stop
+ * byte are ignored (protocol.Binary.Decode reads one value).  DataEncoding validation
+ * (validateProto) stays with the caller.
+ *
+ * Field mapping: the inverse of the row writers (oracle/thrift_binary.py restates them),
+ * following the get*InfoMap functions.  An absent field is Go's GetX() zero.  Fields the
+ * records do not keep are parsed over and dropped: the event blobs and their encodings,
+ * StartedIdentity, the Retry*Last* fields, and the Details / DomainID columns (never passed).
+ *   ActivityInfo (sqlblobs.thrift:136-168): 10 version, 12 scheduled_event_batch_id, 18
+ *     scheduled_time, 20 started_id, 26 StartedTimeNanos, 28 activity_id, 30 request_id, 32 s2s,
+ *     34 s2c, 36 stc, 38 hb, 40 CDR_AI_CANCEL_REQUESTED, 42 cancel_request_id, 44
+ *     timer_task_status, 46 attempt, 48 task_list, 52 CDR_AI_HAS_RETRY, 54 / 56 / 58 initial /
+ *     maximum interval / maximum attempts, 60 expiration_time, 62 backoff_coefficient (the bits),
+ *     64 nonretriable; schedule_id is the key column.
+ *     Times: CDR_AI_STARTED_TIME_SET is set iff field 26's value != CDR_ZERO_TIME_NANOS and
+ *     started_time is that value, else 0 — an absent field 26 decodes as set with 0,
+ *     time.Unix(0, 0) as in Go.  last_heartbeat_time is the act_heartbeat column if it is !=
+ *     CDR_ZERO_TIME_NANOS, else 0; CDR_AI_HEARTBEAT_TIME_SET is set iff it is non-zero and
+ *     STARTED is not set: a row cdr_sync_activity_async left with both bits comes back with
+ *     STARTED alone, which sync.hip and the replay read the same way.
+ *   TimerInfo (:201-206): 10 version, 12 started_id, 14 expiry_time, 16 task_id; timer_id is the
+ *     handle of the key column's string.
+ *   ChildExecutionInfo (:170-184): 10 version, 12 initiated_event_batch_id, 14 started_id, 20
+ *     started_workflow_id, 22 StartedRunID, 28 CreateRequestID, 30 domain_name, 32 workflow_type,
+ *     35 parent_close_policy; initiated_id is the key column.
+ *   RequestCancelInfo (:195-199): 10 version, 11 initiated_event_batch_id, 12 CancelRequestID.
+ *   SignalInfo (:186-193): 10 version, 11 initiated_event_batch_id, 12 SignalRequestID, 14
+ *     signal_name, 16 input, 18 control (absent or empty: handle 0).
+ * Request IDs (CancelRequestID, CreateRequestID, SignalRequestID) are kept as 128 bits: exactly
+ * the canonical lowercase 36-character RFC 4122 text the encoders emit is accepted (hi then lo);
+ * anything else, an absent field included, is CDR_LOAD_E_UUID — the record cannot hold it.
+ * Child StartedRunID follows sqldb.UUID(b).String() (:455): an absent or empty binary is handle
+ * 0; 16 bytes are rendered as canonical lowercase text into gen_bytes (36 bytes at 36 * the
+ * child row's index) and interned, so the handle equals that of the same run ID seen in a
+ * history; any other length is CDR_LOAD_E_UUID.  RetryNonRetryableErrors: a non-empty
+ * list<string> is interned by the bytes of its list body (the encoders' and the ingest's
+ * convention); an empty list or another element type is handle 0.
+ *
+ * Interning is the ingest's: seed i keeps handle i (seed 0 = ""), every other distinct string
+ * gets n_seeds + its rank by cdr_str_hash, handle 0 is "".  Timer IDs from the key column are
+ * interned like any other string, so equal timer IDs in two entries, or in a later ingest
+ * seeded with this table, share a handle.  Only the last occurrence of a repeated field is
+ * interned, and only the rows of entries in which every row decoded (a duplicate key does not
+ * take an entry's strings out).  str_ref is cdr_ingest_out's with one more source: bit 63 =
+ * offset into seed_bytes, bit 62 = offset into gen_bytes, else offset into `bytes`.
+ *
+ * Order.  Each entry's rows are written in ascending (signed) key order — the timer key is the
+ * handle as an integer — whatever order they arrive in: the order every replay path writes and
+ * cdr_carry / cdr_mutation_async require.  Two rows of one entry and table with the same key
+ * are both CDR_LOAD_E_DUP_KEY (checked for entries in which every row decoded).  The ranking
+ * compares every row of an entry with every other row of its table, so an entry may hold at
+ * most CDR_LOAD_MAX_ENTRY_ROWS rows per table (the reference's pending tables hold tens): in a
+ * larger one every row of that table is CDR_LOAD_E_ENTRY_ROWS and the entry fails, which bounds
+ * the kernel's time whatever the caller passes.
+ *
+ * Failure.  As in Go, one bad row fails the whole GetWorkflowExecution: entry_status[w] is the
+ * status of the entry's first failing row (lowest table, then lowest row), state.result[w].code
+ * is CDR_E_LOAD_ROWS, its n_* are 0 and its table slices are unspecified; other entries are
+ * unaffected.  Row statuses are the CDR_DEC_* codes of cdr/ingest.h plus the two below.
+ *
+ * Inputs (device pointers): `bytes` holds every blob and every timer-ID string; table t has
+ * n_rows[t] rows, row r's blob at bytes[blob_off[t][r], blob_off[t][r+1]) and entry w's rows at
+ * [entry_row0[t][w], entry_row0[t][w+1]); key[t] is schedule_id (t = 0) or initiated_id (t =
+ * 2..4) per row, key[1] is not read: timer row r's ID is bytes[timer_id_off[r],
+ * timer_id_off[r+1]); act_heartbeat[r] is the LastHeartbeatUpdatedTime column as UnixNano
+ * (CDR_ZERO_TIME_NANOS: Go's zero time); seeds as in cdr_ingest_in.  Offsets past n_bytes are
+ * clamped: no byte outside [bytes, bytes + n_bytes) is read.
+ *
+ * Outputs live in the context's grow-only workspace (slots of their own: a later
+ * cdr_ingest_decode does not touch them) and stay valid until the next cdr_load_rows on the
+ * context: `state` is a cdr_out view with the five pending tables ([n_rows[t]] records) and
+ * result[n_entries] filled, exec / repl / vh / rp / sa and the task pointers NULL; caps[w]
+ * (device) has *_off = entry_row0[t][w], *_cap = the entry's row count and everything else 0;
+ * totals = the row counts.  All-empty tables and zero entries are valid.  No allocation once
+ * the workspace is warm.  Synchronous on `stream` (the string count sizes the table).
+ * CDR_API_EINVAL for null arguments, n_seeds == 0, or rows without entries. */
+#define CDR_LOAD_E_UUID 16    /* a request ID that is not canonical UUID text / a run ID that is not 0 or 16 bytes */
+#define CDR_LOAD_E_DUP_KEY 17 /* two rows of one entry and table share a key */
+#define CDR_LOAD_E_ENTRY_ROWS 18 /* more than CDR_LOAD_MAX_ENTRY_ROWS rows of one entry in one table */
+#define CDR_LOAD_MAX_ENTRY_ROWS 16384u
+#define CDR_LOAD_TABLES 5
+typedef struct cdr_rows_in { /* device pointers */
+  const uint8_t* bytes;
+  uint64_t n_bytes;
+  const uint64_t* blob_off[CDR_LOAD_TABLES];   /* [n_rows[t] + 1] */
+  const uint32_t* entry_row0[CDR_LOAD_TABLES]; /* [n_entries + 1] */
+  const int64_t* key[CDR_LOAD_TABLES];         /* [n_rows[t]]; key[1] unused */
+  const uint64_t* timer_id_off;                /* [n_rows[1] + 1] */
+  const int64_t* act_heartbeat;                /* [n_rows[0]] */
+  const uint8_t* seed_bytes;
+  const uint64_t* seed_off;                    /* [n_seeds + 1]; seed 0 must be "" */
+  uint32_t n_rows[CDR_LOAD_TABLES];
+  uint32_t n_entries, n_seeds, _pad;
+} cdr_rows_in;
+typedef struct cdr_rows_out { /* device buffers owned by the context */
+  cdr_out state;
+  cdr_wf_caps* caps;     /* [n_entries] */
+  cdr_totals totals;
+  int32_t* row_status[CDR_LOAD_TABLES]; /* [n_rows[t]] */
+  int32_t* entry_status; /* [n_entries] */
+  uint64_t* str_ref;     /* [n_strings] */
+  uint32_t* str_len;     /* [n_strings] */
+  uint8_t* gen_bytes;    /* [n_gen_bytes] = 36 * n_rows[2] */
+  uint64_t n_gen_bytes;
+  uint32_t n_strings, n_bad_entries;
+} cdr_rows_out;
+int cdr_load_rows(cdr_ctx* ctx, const cdr_rows_in* in, cdr_rows_out* out, void* stream);
+/* Device milliseconds of the last cdr_load_rows on the context, between HIP events on its
+ * stream: ms[0] the count pass (with the row -> entry map), ms[1] the intern pass and the
+ * string ranking (with the two host round trips that size the table and the sort), ms[2] the
+ * row ranking, ms[3] the fill pass and the entry epilogue.  The call is synchronous and holds
+ * host round trips between its passes, so a caller's own events around it cannot tell the
+ * passes apart; like cdr_last_kernel_ms for the replay, this is how the measurement
+ * (tools/load_bench.py) and a caller's monitoring read them. */
+int cdr_load_pass_ms(cdr_ctx* ctx, float* ms);
+
+/* A decoded string table (cdr_rows_out's, or cdr_ingest_out's with gen_bytes == NULL) as the
+ * contiguous cdr_strtab the encoders take and cdr_ingest_in takes as seeds.  Two calls, as the
+ * encoders: with out_bytes == NULL it writes off[0..n] (device; string h = [off[h], off[h+1]));
+ * the caller reads off[n], allocates out_bytes and calls again with the same `off` to copy the
+ * bytes.  `bytes` is the blob buffer the table was decoded from.  Asynchronous. */
+int cdr_strtab_gather_async(cdr_ctx* ctx, const uint64_t* str_ref, const uint32_t* str_len, uint32_t n,
+                            const uint8_t* bytes, const uint8_t* seed_bytes, const uint8_t* gen_bytes,
+                            uint64_t* off, uint8_t* out_bytes, void* stream);
+
 /* ------------------------------------------------------------------ misc */
 
 /* farmhash Fingerprint32(workflowID) % numShards (common/util.go:249-252) */

@@ -187,8 +187,11 @@ enum cdr_status {
   CDR_P_UNKNOWN_CLUSTER = 35,       /* ClusterNameForFailoverVersion panic metadata.go:193-200 */
   CDR_P_UNKNOWN_WF_STATE = 36,      /* IsWorkflowExecutionRunning panic mutableStateBuilder.go:1432-1433 */
   CDR_NOT_APPLIED = 64,             /* new-run history never applied (parent stopped first) */
-  CDR_NOT_RUN = 65                  /* skipped entry of a masked launch (cdr_dev_batch.skip): the
+  CDR_NOT_RUN = 65,                 /* skipped entry of a masked launch (cdr_dev_batch.skip): the
                                        record was not replayed this time (cdr_ndc_replicate_async) */
+  CDR_E_LOAD_ROWS = 66              /* cdr_load_rows: one of the entry's persisted rows did not decode (the
+                                       error GetWorkflowExecution returns, workflowStateMaps.go:160-164);
+                                       entry_status says which way */
 };
 /* cdr_wf_result.flags */
 #define CDR_RF_IN_NEWRUN 0x1u      /* error raised while replaying newRunHistory */

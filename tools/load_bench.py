@@ -1,0 +1,206 @@
+#!/usr/bin/env python3
+"""Throughput of the persisted-row loader (cdr_load_rows) beside the history ingest
+(cdr_ingest_decode), the comparable lane-per-blob thrift walk, on the same populations.
+
+States: the final states of a config-3 and a config-5 replay.  --base workflows are
+generated, replayed on the GPU and encoded on the host side of the encoders
+(rows.encode_state walks every row in Python), then tiled --tile times on the way to the
+device, so the loader runs over base * tile workflows (1M by default).  Tiling repeats the
+strings: the loader interns base-many distinct strings however many rows name them, as a
+store full of shared task lists and types would, but the per-workflow IDs of a real store
+would add distinct strings the tiles do not have: a second run appends the entry number to
+every timer ID, which makes the timer table's key strings distinct per workflow.  Seeds: "" alone, so every string is new.
+
+Each call is timed wall-clock (it is synchronous) on a warm context over --reps repeats;
+the passes inside it by the HIP events cdr_load_pass_ms reads.  The ingest decodes the same
+base population's history blobs, tiled up to --ingest-bytes, in the same process.
+Writes one JSON record (--out).
+
+    python tools/load_bench.py --out profiles/load_rows.json
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from cadence_amd import abi, engine, ingest, rows  # noqa: E402
+
+PASSES = ("count", "intern_and_rank_strings", "rank_rows", "fill_and_epilogue")
+
+
+def tile_offsets(off: np.ndarray, tile: int, base: int, dtype) -> np.ndarray:
+    """`tile` copies of a run of n contiguous items (off: n + 1 offsets), back to back from `base`."""
+    n, span = len(off) - 1, int(off[-1] - off[0])
+    rel = (off[:-1] - off[0]).astype(np.int64)
+    out = np.empty(n * tile + 1, dtype)
+    out[:-1] = (rel[None, :] + (np.arange(tile, dtype=np.int64) * span)[:, None]).reshape(-1) + base
+    out[-1] = base + span * tile
+    return out
+
+
+def tile_rows(R: rows.Rows, tile: int) -> rows.Rows:
+    """The rows `tile` times over: each table's blobs stay contiguous, timer IDs follow."""
+    segs, offs, row0, keys, pos = [], [], [], [], 0
+    for t in range(5):
+        o = R.blob_off[t]
+        seg = R.bytes[int(o[0]):int(o[-1])]
+        offs.append(tile_offsets(o, tile, pos, np.uint64))
+        segs.append(np.tile(seg, tile))
+        pos += len(seg) * tile
+        row0.append(tile_offsets(R.entry_row0[t], tile, 0, np.uint32))
+        keys.append(np.tile(R.key[t], tile))
+    o = R.timer_id_off
+    tid = tile_offsets(o, tile, pos, np.uint64)
+    segs.append(np.tile(R.bytes[int(o[0]):int(o[-1])], tile))
+    return rows.Rows(np.concatenate(segs), offs, row0, keys, tid, np.tile(R.act_heartbeat, tile), R.n_entries * tile)
+
+
+def stats(xs) -> dict:
+    xs = sorted(float(x) for x in xs)
+    return {"median": float(np.median(xs)), "min": xs[0], "max": xs[-1]}
+
+
+def distinct_timer_ids(R: rows.Rows) -> rows.Rows:
+    """The rows with every timer ID made its workflow's own (the entry number appended): the
+    timer table's key strings are then distinct per workflow, as IDs in a real store are."""
+    lo = int(R.timer_id_off[0])
+    entry = np.repeat(np.arange(R.n_entries), np.diff(R.entry_row0[1].astype(np.int64)))
+    ids = [R.timer_id(r) + b"#%07d" % w for r, w in enumerate(entry.tolist())]
+    off = np.zeros(len(ids) + 1, np.uint64)
+    off[1:] = np.cumsum([len(s) for s in ids])
+    data = np.concatenate([R.bytes[:lo], np.frombuffer(b"".join(ids) or b"\0", np.uint8)])
+    return rows.Rows(data[:lo + int(off[-1])], R.blob_off, R.entry_row0, R.key, off + np.uint64(lo), R.act_heartbeat,
+                     R.n_entries)
+
+
+def time_load(eng, R: rows.Rows, reps: int) -> dict:
+    """cdr_load_rows over R (seeds: "" alone), wall clock and passes."""
+    L = abi.lib()
+    n_rows, n_bytes = R.n_rows, int(len(R.bytes))
+    dev = rows.DeviceBuffers()
+    try:
+        sb, so = ingest.string_table([b""])
+        inp = abi.CdrRowsIn()
+        inp.bytes, inp.n_bytes = dev.up(R.bytes), n_bytes
+        for t in range(5):
+            inp.blob_off[t], inp.entry_row0[t] = dev.up(R.blob_off[t]), dev.up(R.entry_row0[t])
+            inp.key[t] = dev.up(R.key[t]) if t != 1 else None
+            inp.n_rows[t] = n_rows[t]
+        inp.timer_id_off, inp.act_heartbeat = dev.up(R.timer_id_off), dev.up(R.act_heartbeat)
+        inp.seed_bytes, inp.seed_off = dev.up(sb), dev.up(so)
+        inp.n_entries, inp.n_seeds = R.n_entries, 1
+        wall, passes = [], [[] for _ in PASSES]
+        res = abi.CdrRowsOut()
+        for rep in range(reps + 1):
+            assert dev.hip.hipDeviceSynchronize() == 0
+            t0 = time.perf_counter()
+            rc = L.cdr_load_rows(eng.ctx, C.byref(inp), C.byref(res), None)
+            t1 = time.perf_counter()
+            assert rc == 0 and res.n_bad_entries == 0, (rc, res.n_bad_entries)
+            ms = (C.c_float * 4)()
+            assert L.cdr_load_pass_ms(eng.ctx, ms) == 0
+            if rep:  # the first call grows the workspace
+                wall.append(t1 - t0)
+                for i in range(4):
+                    passes[i].append(ms[i] / 1e3)
+        n_strings = int(res.n_strings)
+    finally:
+        dev.free()
+    total_rows = sum(n_rows)
+    w = stats(wall)
+    rec = {"bytes": n_bytes, "strings": n_strings, "load_wall_s": w, "load_gbs": n_bytes / w["median"] / 1e9,
+           "load_rows_per_s": total_rows / w["median"], "passes": {}}
+    for name, xs in zip(PASSES, passes):
+        s = stats(xs)
+        rec["passes"][name] = {"s": s, "rows_per_s": total_rows / s["median"]}
+        if name != "rank_rows":  # (it reads keys, not blob bytes)
+            rec["passes"][name]["gbs"] = n_bytes / s["median"] / 1e9
+    return rec
+
+
+def bench_config(eng, cfg: int, base: int, tile: int, reps: int, ingest_bytes: int) -> dict:
+    L = abi.lib()
+    b = engine.synth_batch(cfg, base, seed=0x5EED0000 + cfg)
+    out = eng.replay(b)
+    strs = rows.state_strings(b, out)
+    R = tile_rows(rows.encode_state(eng, b, out, strs), tile)
+    rec = {"config": cfg, "workflows": R.n_entries, "base_workflows": base, "tile": tile,
+           "rows": dict(zip(rows.TABLES, R.n_rows)), "rows_total": sum(R.n_rows)}
+    rec.update(time_load(eng, R, reps))
+    # the same rows with the timer IDs distinct per workflow: the intern pass inserts and the
+    # ranking sorts millions of strings instead of finding a few thousand again and again
+    rec["distinct_timer_ids"] = time_load(eng, distinct_timer_ids(R), reps)
+    # ---- the history ingest of the same population
+    enc = ingest.encode_batch(b, threads=16)
+    raw = enc.blob_bytes[:int(enc.blob_off[-1])]
+    itile = max(1, min(tile, ingest_bytes // max(1, len(raw))))
+    dev = rows.DeviceBuffers()
+    try:
+        sb, so = ingest.string_table(enc.seeds)
+        dm = np.array(enc.domain_map, np.uint32).reshape(-1) if enc.domain_map else np.zeros(2, np.uint32)
+        ii = abi.CdrIngestIn()
+        ii.blob_bytes = dev.up(np.tile(raw, itile))
+        ii.blob_off = dev.up(tile_offsets(enc.blob_off, itile, 0, np.uint64))
+        ii.entry_blob0 = dev.up(tile_offsets(enc.entry_blob0, itile, 0, np.uint32))
+        ii.seed_bytes, ii.seed_off, ii.domain_map = dev.up(sb), dev.up(so), dev.up(dm)
+        ii.n_blobs, ii.n_entries = (len(enc.blob_off) - 1) * itile, b.n_wfs * itile
+        ii.n_seeds, ii.n_domains = len(enc.seeds), len(enc.domain_map)
+        dec = []
+        for rep in range(reps + 1):
+            io = abi.CdrIngestOut()
+            assert dev.hip.hipDeviceSynchronize() == 0
+            t0 = time.perf_counter()
+            rc = L.cdr_ingest_decode(eng.ctx, C.byref(ii), C.byref(io), None)
+            t1 = time.perf_counter()
+            assert rc == 0 and io.n_bad_blobs == 0, (rc, io.n_bad_blobs)
+            if rep:
+                dec.append(t1 - t0)
+        d = stats(dec)
+        rec["ingest"] = {"workflows": b.n_wfs * itile, "tile": itile, "blobs": int(ii.n_blobs),
+                         "bytes": len(raw) * itile, "events": int(io.n_events), "strings": int(io.n_strings),
+                         "decode_wall_s": d, "decode_gbs": len(raw) * itile / d["median"] / 1e9}
+    finally:
+        dev.free()
+    return rec
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--configs", default="3,5")
+    ap.add_argument("--base", type=int, default=10_000)
+    ap.add_argument("--tile", type=int, default=100)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--ingest-bytes", type=int, default=2_000_000_000)
+    ap.add_argument("--out", default="")
+    args = ap.parse_args()
+    try:
+        import torch
+        box = torch.cuda.get_device_name(0)
+    except Exception:  # noqa: BLE001
+        box = "unknown"
+    eng = engine.Engine(0)
+    rec = {"tool": "tools/load_bench.py", "device": box, "libcdr": abi.lib().cdr_version().decode(),
+           "build_flags": int(abi.lib().cdr_build_flags()), "reps": args.reps,
+           "timing": "wall clock around the synchronous calls on a warm context (first call dropped); passes: HIP "
+                     "events inside cdr_load_rows (the intern interval holds its two host round trips)",
+           "seeds": 1, "configs": []}
+    for cfg in (int(c) for c in args.configs.split(",")):
+        r = bench_config(eng, cfg, args.base, args.tile, args.reps, args.ingest_bytes)
+        rec["configs"].append(r)
+        print(json.dumps(r), flush=True)
+    eng.close()
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(rec, f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
