@@ -220,6 +220,16 @@ CdrRowsOut = _S("cdr_rows_out", [
     ("state", CdrOut), ("caps", C.c_void_p), ("totals", CdrTotals), ("row_status", C.c_void_p * LOAD_TABLES),
     ("entry_status", C.c_void_p), ("str_ref", C.c_void_p), ("str_len", C.c_void_p), ("gen_bytes", C.c_void_p),
     ("n_gen_bytes", u64), ("n_strings", u32), ("n_bad_entries", u32)])
+# whole stored states (cdr.h cdr_load_state): the execution rows' inputs and extra outputs
+LOAD_E_ENCODING, LOAD_E_SHAPE, LOAD_E_CLUSTER = 19, 20, 21
+LOAD_MAX_VH_ITEMS, LOAD_MAX_RESET_POINTS, LOAD_MAX_SEARCH_ATTR = 16384, 1024, 256
+LOAD_STATUS.update({19: "E_ENCODING", 20: "E_SHAPE", 21: "E_CLUSTER"})
+CdrExecRowsIn = _S("cdr_exec_rows_in", [
+    ("blob_off", C.c_void_p), ("domain_id", C.c_void_p), ("run_id", C.c_void_p), ("workflow_id_off", C.c_void_p),
+    ("next_event_id", C.c_void_p), ("last_write_version", C.c_void_p), ("cluster_seed", u32 * MAX_CLUSTERS),
+    ("n_clusters", u32), ("_pad", u32)])
+CdrStateOut = _S("cdr_state_out", [
+    ("rows", CdrRowsOut), ("persist", C.c_void_p), ("builder", C.c_void_p), ("exec_status", C.c_void_p)])
 CdrOpts = _S("cdr_opts", [("plan_mode", u32), ("fast_path", i32), ("reg_path", i32), ("concurrent", i32),
                           ("workspace_bytes", u64)])
 CdrVHToken = _S("cdr_vh_token", [("tree", u32), ("_pad", u32), ("branch_lo", u64), ("branch_hi", u64)])
@@ -377,6 +387,7 @@ MIRRORS = {
     "cdr_mut_info": CdrMutInfo, "cdr_mutation": CdrMutation,
     "cdr_sync_activity": CdrSyncActivity, "cdr_sync_result": CdrSyncResult,
     "cdr_rows_in": CdrRowsIn, "cdr_rows_out": CdrRowsOut,
+    "cdr_exec_rows_in": CdrExecRowsIn, "cdr_state_out": CdrStateOut,
 }
 
 # C ABI entry points declared in include/cdr/cdr.h and include/cdr/synth.h
@@ -460,6 +471,8 @@ EXPORTS = {
     "cdr_ingest_plan": (i32, [C.c_void_p, C.POINTER(CdrIngestOut), C.POINTER(CdrBatch), u32, C.POINTER(CdrDevBatch),
                               C.c_void_p, C.POINTER(CdrTotals), C.c_void_p]),
     "cdr_load_rows": (i32, [C.c_void_p, C.POINTER(CdrRowsIn), C.POINTER(CdrRowsOut), C.c_void_p]),
+    "cdr_load_state": (i32, [C.c_void_p, C.POINTER(CdrRowsIn), C.POINTER(CdrExecRowsIn), C.POINTER(CdrStateOut),
+                             C.c_void_p]),
     "cdr_load_pass_ms": (i32, [C.c_void_p, C.POINTER(C.c_float)]),
     "cdr_strtab_gather_async": (i32, [C.c_void_p, C.c_void_p, C.c_void_p, u32, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p]),

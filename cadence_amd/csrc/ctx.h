@@ -58,6 +58,9 @@ enum cdr_ws_slot {
   WS_LD_ACT, WS_LD_TIMER, WS_LD_CHILD, WS_LD_CANCEL, WS_LD_SIGNAL, WS_LD_GEN, WS_LD_TABKEY, WS_LD_TABVAL,
   WS_LD_TABREF, WS_LD_TABLEN, WS_LD_SKEY, WS_LD_SKEY2, WS_LD_SIDX, WS_LD_SIDX2, WS_LD_STRREF, WS_LD_STRLEN,
   WS_LD_MISC, WS_LD_CCOUNT, WS_LD_COFFS, WS_LD_CTMP, WS_LD_SORTTMP,
+  // cdr_load_state: the execution rows' records, item tables, per-entry counts and their scan
+  WS_LD_EXEC, WS_LD_REPL, WS_LD_PERSIST, WS_LD_BUILDER, WS_LD_XSTATUS, WS_LD_VH, WS_LD_RP, WS_LD_SA, WS_LD_NSA,
+  WS_LD_XCNT, WS_LD_XOFF, WS_LD_XTMP,
   WS_GATHER_TMP,  // cdr_strtab_gather_async: the offset scan's temporary storage
   WS_NUM
 };

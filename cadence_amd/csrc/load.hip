@@ -1,6 +1,7 @@
-// load.hip — on-device decode of the SQL persistence's pending-table row blobs into the
-// loaded-state tables cdr_carry takes (cdr.h "loading persisted rows"): the inverse of
-// encode.hip / encode_var.hip for the five pending tables.
+// load.hip — on-device decode of the SQL persistence's row blobs into the loaded states
+// cdr_carry takes (cdr.h "loading persisted rows"): the inverse of encode.hip / encode_var.hip
+// for the five pending tables (cdr_load_rows) and, with them, the execution row
+// (cdr_load_state; "the execution rows" below).
 //
 // One lane per row, one parser template per table (the pass is its parameter, so the passes
 // agree on every byte); each wavefront stages its 64 consecutive rows' bytes in LDS first
@@ -407,6 +408,589 @@ __global__ __launch_bounds__(CDR_LOAD_BLOCK) void k_rows(LCtx C) {
   }
 }
 
+// ---------------------------------------------------------------- the execution rows
+// One lane per entry, the same three passes (cdr.h cdr_load_state).  The walk of the row records
+// its scalars and where its strings, maps and nested blobs are; every pass then derives the
+// status, the builder and the item counts again from those, level by level through the nested
+// blobs (a level's walk has skipped, and so checked, everything below it), and names each
+// handle field in the same order: COUNT counts them and the entry's gen_bytes need, INTERN
+// inserts them (UUID texts and the Memo body written into the entry's share of gen_bytes
+// first), FILL looks them up and stores the records whole.
+struct XCnt {  // per entry: version-history items, reset points, search-attribute rows, gen bytes
+  uint64_t v[4];
+};
+struct XCntAdd {
+  __host__ __device__ __forceinline__ XCnt operator()(const XCnt& a, const XCnt& b) const {
+    return XCnt{{a.v[0] + b.v[0], a.v[1] + b.v[1], a.v[2] + b.v[2], a.v[3] + b.v[3]}};
+  }
+};
+
+struct XCtx {
+  const uint8_t* bytes;
+  uint64_t total;
+  cdr_exec_rows_in in;
+  const uint8_t* seed_bytes;
+  const uint64_t* seed_off;
+  uint32_t n_seeds, n_entries;
+  unsigned long long* fail;
+  STab T;
+  int32_t* status;             // [n_entries]
+  unsigned long long* totals;  // COUNT: string fields
+  XCnt* cnt;                   // COUNT writes
+  const XCnt* off;             // its exclusive scan, [n_entries + 1]
+  uint8_t* gen;                // the execution rows' part of gen_bytes, at offset gen_base
+  uint64_t gen_base;
+  cdr_exec_info* exec;
+  cdr_repl_state* repl;
+  cdr_exec_persist* persist;
+  uint32_t* builder;
+  cdr_vh_item* vh;
+  cdr_reset_point* rp;
+  cdr_kv* sa;
+  uint32_t* n_sa;  // FILL: distinct search-attribute keys, for the epilogue
+};
+
+struct U16 {  // 16 bytes, big-endian
+  uint64_t hi, lo;
+};
+__device__ __forceinline__ U16 u16_at(Rd& r, uint64_t at) {
+  U16 u{0, 0};
+  for (uint32_t i = 0; i < 8; i++) u.hi = (u.hi << 8) | r.at(at + i);
+  for (uint32_t i = 8; i < 16; i++) u.lo = (u.lo << 8) | r.at(at + i);
+  return u;
+}
+__device__ __forceinline__ U16 u16_col(const uint8_t* p) {
+  U16 u{0, 0};
+  for (uint32_t i = 0; i < 8; i++) u.hi = (u.hi << 8) | p[i];
+  for (uint32_t i = 8; i < 16; i++) u.lo = (u.lo << 8) | p[i];
+  return u;
+}
+__device__ __forceinline__ uint32_t u16_char(U16 u, uint32_t i) {  // character i of UUID(b).String()
+  if (i == 8 || i == 13 || i == 18 || i == 23) return '-';
+  const uint32_t d = i - (i > 8 ? 1u : 0u) - (i > 13 ? 1u : 0u) - (i > 18 ? 1u : 0u) - (i > 23 ? 1u : 0u);
+  const uint32_t nib = (uint32_t)(((d < 16 ? u.hi : u.lo) >> (60u - 4u * (d & 15u))) & 15u);
+  return nib < 10 ? '0' + nib : 'a' + (nib - 10);
+}
+__device__ __forceinline__ uint64_t u16_hash(U16 u) {  // cdr_str_hash of that text
+  uint64_t h = 0xCBF29CE484222325ull;
+  for (uint32_t i = 0; i < GEN_BYTES; i++) h = (h ^ u16_char(u, i)) * 0x100000001B3ull;
+  h = cdr_mix64(h ^ ((uint64_t)GEN_BYTES * 0x9E3779B97F4A7C15ull));
+  return h ? h : 1u;
+}
+// cdr_str_hash of a Memo struct's wire body around the map body m (0D 00 0A, m, 00); the
+// bytes go to `out` as well when it is not null
+__device__ uint64_t memo_hash(Rd& r, Span m, uint8_t* out) {
+  uint64_t h = 0xCBF29CE484222325ull;
+  const uint64_t n = (uint64_t)m.n + 4;
+  for (uint64_t i = 0; i < n; i++) {
+    const uint32_t c = i == 0 ? 0x0Du : i == 2 ? 0x0Au : (i == 1 || i == n - 1) ? 0u : r.at(m.at + (i - 3));
+    h = (h ^ c) * 0x100000001B3ull;
+    if (out) out[i] = (uint8_t)c;
+  }
+  h = cdr_mix64(h ^ (n * 0x9E3779B97F4A7C15ull));
+  return h ? h : 1u;
+}
+
+__device__ __forceinline__ Rd sub_reader(const Rd& r, uint64_t at, uint64_t n) {  // over [at, at + n) of the same bytes
+  Rd q = r;
+  q.pos = at;
+  q.end = at + n;
+  q.err = CDR_DEC_OK;
+  return q;
+}
+// a list field: element type, count and the bytes of its body (the value skipped, so checked);
+// another wire type is skipped and an earlier occurrence stays
+__device__ __forceinline__ void f_list(Rd& r, uint32_t t, uint32_t* et, uint32_t* cnt, Span* body) {
+  if (t != T_LIST) {
+    skip1(r, t);
+    return;
+  }
+  const uint64_t at = r.pos;
+  const uint32_t e = r.u8();
+  const uint32_t c = (uint32_t)r.size();
+  if (!r.ok()) return;
+  r.pos = at;
+  skip(r, T_LIST);
+  if (!r.ok()) return;
+  *et = e;
+  *cnt = c;
+  *body = Span{at, (uint32_t)(r.pos - at)};
+}
+__device__ __forceinline__ bool f_map(Rd& r, uint32_t t, Span* body) {
+  if (t != T_MAP) {
+    skip1(r, t);
+    return false;
+  }
+  const uint64_t at = r.pos;
+  skip(r, T_MAP);
+  if (!r.ok()) return false;
+  *body = Span{at, (uint32_t)(r.pos - at)};
+  return true;
+}
+__device__ __forceinline__ bool is_thriftrw(Rd& r, Span s) {
+  const char* k = "thriftrw";
+  if (s.n != 8) return false;
+  bool same = true;
+  for (uint32_t i = 0; i < 8; i++) same = same && r.at(s.at + i) == (uint32_t)k[i];
+  return same;
+}
+
+// a branch token: 0x59, HistoryBranch{10 TreeID, 20 BranchID, 30 Ancestors}
+struct Tok {
+  Span tree;
+  uint64_t lo, hi;
+};
+__device__ int32_t parse_token(Rd& r, Span s, Tok* out) {
+  if (s.n == 0 || r.at(s.at) != 0x59u) return CDR_LOAD_E_ENCODING;
+  Rd q = sub_reader(r, s.at + 1, s.n - 1);
+  Span tree{0, 0}, bid{0, 0}, anc{0, 0};
+  uint32_t et = 0, n_anc = 0;
+  fields(q, [&](uint32_t t, uint32_t id) {
+    switch (id) {
+      case 10: f_str(q, t, &tree); break;
+      case 20: f_str(q, t, &bid); break;
+      case 30: f_list(q, t, &et, &n_anc, &anc); break;
+      default: skip1(q, t); break;
+    }
+  });
+  if (q.err) return q.err;
+  if (n_anc) return CDR_LOAD_E_SHAPE;
+  if (!parse_uuid(r, bid, &out->lo, &out->hi)) return CDR_LOAD_E_UUID;
+  out->tree = tree;
+  return CDR_DEC_OK;
+}
+
+enum : uint32_t { X_PARENT = 1, X_F18 = 2, X_F44 = 4, X_TOKEN = 8, X_SA = 16, X_MEMO = 32, X_VH = 64 };
+
+struct XRow {  // what the walk of one execution row leaves
+  cdr_exec_info x;
+  cdr_exec_persist ps;
+  int64_t f44, f80, f82, f94, f106;
+  uint32_t has;
+  Span pdom, pwf, prun, tl, wt, ctx, crq, drq, stl, nonret, cron, token, clv, cfv, cimpl;
+  Span rpb, rpenc, vhb, vhenc, lri, sam, memo;
+
+  __device__ __forceinline__ void parse(Rd& r) {
+    {
+      uint64_t* z = reinterpret_cast<uint64_t*>(&x);
+#pragma unroll
+      for (uint32_t i = 0; i < sizeof(x) / 8; i++) z[i] = 0;
+      z = reinterpret_cast<uint64_t*>(&ps);
+#pragma unroll
+      for (uint32_t i = 0; i < sizeof(ps) / 8; i++) z[i] = 0;
+    }
+    f44 = f80 = f82 = f94 = f106 = 0;
+    has = 0;
+    pdom = pwf = prun = tl = wt = ctx = crq = drq = stl = nonret = cron = token = clv = cfv = cimpl = Span{0, 0};
+    rpb = rpenc = vhb = vhenc = lri = sam = memo = Span{0, 0};
+    auto present = [&](uint32_t t, uint32_t want, uint32_t bit) { has |= t == want ? bit : 0u; };
+    fields(r, [&](uint32_t t, uint32_t id) {
+      switch (id) {
+        case 10: present(t, T_STRING, X_PARENT); f_str(r, t, &pdom); break;
+        case 12: f_str(r, t, &pwf); break;
+        case 14: f_str(r, t, &prun); break;
+        case 16: f_i64(r, t, &x.initiated_id); break;
+        case 18: present(t, T_I64, X_F18); f_i64(r, t, &x.completion_event_batch_id); break;
+        case 24: f_str(r, t, &tl); break;
+        case 26: f_str(r, t, &wt); break;
+        case 28: f_i32(r, t, &x.workflow_timeout); break;
+        case 30: f_i32(r, t, &x.decision_timeout_value); break;
+        case 32: f_str(r, t, &ctx); break;
+        case 34: f_i32(r, t, &x.state); break;
+        case 36: f_i32(r, t, &x.close_status); break;
+        case 38: f_i64(r, t, &ps.start_version); break;
+        case 40: f_i64(r, t, &ps.current_version); break;
+        case 44: present(t, T_I64, X_F44); f_i64(r, t, &f44); break;
+        case 46: f_map(r, t, &lri); break;
+        case 50: f_i64(r, t, &x.last_first_event_id); break;
+        case 52: f_i64(r, t, &x.last_processed_event); break;
+        case 54: f_i64(r, t, &ps.start_time); break;
+        case 56: f_i64(r, t, &ps.last_updated_time); break;
+        case 58: f_i64(r, t, &x.decision_version); break;
+        case 60: f_i64(r, t, &x.decision_schedule_id); break;
+        case 62: f_i64(r, t, &x.decision_started_id); break;
+        case 64: f_i32(r, t, &x.decision_timeout); break;
+        case 66: f_i64(r, t, &x.decision_attempt); break;
+        case 68: f_i64(r, t, &x.decision_started_ts); break;
+        case 69: f_i64(r, t, &x.decision_scheduled_ts); break;
+        case 70: f_bool(r, t, &x.flags, CDR_XI_CANCEL_REQUESTED); break;
+        case 71: f_i64(r, t, &x.decision_original_scheduled_ts); break;
+        case 72: f_str(r, t, &crq); break;
+        case 74: f_str(r, t, &drq); break;
+        case 78: f_str(r, t, &stl); break;
+        case 80: f_i64(r, t, &f80); break;
+        case 82: f_i64(r, t, &f82); break;
+        case 84: f_i32(r, t, &x.initial_interval); break;
+        case 86: f_i32(r, t, &x.maximum_interval); break;
+        case 88: f_i32(r, t, &x.maximum_attempts); break;
+        case 90: f_i32(r, t, &x.expiration_seconds); break;
+        case 92:
+          if (t == T_DOUBLE) x.backoff_coefficient = __longlong_as_double((long long)r.be64());
+          else skip1(r, t);
+          break;
+        case 94: f_i64(r, t, &f94); break;
+        case 96: {  // RetryNonRetryableErrors: the list's bytes; empty / not strings -> 0
+          uint32_t et = T_STRING, cnt = 0;
+          Span body{0, 0};
+          const bool lst = t == T_LIST;
+          f_list(r, t, &et, &cnt, &body);
+          if (lst && r.ok()) nonret = (et == T_STRING && cnt > 0) ? body : Span{0, 0};
+          break;
+        }
+        case 98: f_bool(r, t, &x.flags, CDR_XI_HAS_RETRY); break;
+        case 100: f_str(r, t, &cron); break;
+        case 104: present(t, T_STRING, X_TOKEN); f_str(r, t, &token); break;
+        case 106: f_i64(r, t, &f106); break;
+        case 108: f_i64(r, t, &ps.history_size); break;
+        case 110: f_str(r, t, &clv); break;
+        case 112: f_str(r, t, &cfv); break;
+        case 114: f_str(r, t, &cimpl); break;
+        case 115: f_str(r, t, &rpb); break;
+        case 116: f_str(r, t, &rpenc); break;
+        case 118: has |= f_map(r, t, &sam) ? X_SA : 0u; break;
+        case 120: has |= f_map(r, t, &memo) ? X_MEMO : 0u; break;
+        case 122: present(t, T_STRING, X_VH); f_str(r, t, &vhb); break;
+        case 124: f_str(r, t, &vhenc); break;
+        default: skip1(r, t); break;  // CompletionEvent and its encoding, CancelRequestID, LastEventTaskID
+      }
+    });
+  }
+};
+
+template <class T>
+__device__ __forceinline__ void store_whole(T* dst, const T& v) {
+  const uint64_t* s = reinterpret_cast<const uint64_t*>(&v);
+  uint64_t* o = reinterpret_cast<uint64_t*>(dst);
+#pragma unroll
+  for (uint32_t i = 0; i < sizeof(T) / 8; i++) o[i] = s[i];
+}
+
+template <int P>
+__global__ __launch_bounds__(CDR_LOAD_BLOCK) void k_exec(XCtx C) {
+  const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  LDS3 uint4* stage = (LDS3 uint4*)ld_lds + (uint64_t)wv * (CDR_LOAD_STAGE / 16);
+  uint64_t s_lo, s_n;
+  stage_blobs(C.bytes, C.in.blob_off, C.total, CDR_LOAD_STAGE, C.n_entries, w - lane, lane, stage, &s_lo, &s_n);
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  uint64_t n_str = 0;
+  const bool live = w < C.n_entries &&
+                    (P == COUNT || (C.fail[w] == NO_FAIL && (P == INTERN || C.fail[C.n_entries + w] == NO_FAIL)));
+  if (live) {
+    Rd rd;
+    const uint64_t e = umin64(C.in.blob_off[w + 1], C.total), p = umin64(C.in.blob_off[w], e);
+    rd.init(C.bytes, p, e, C.total);
+    rd.sb = (const LDS3 uint8_t*)stage;
+    rd.s_lo = s_lo;
+    rd.s_n = s_n;
+    XRow R;
+    R.parse(rd);
+    int32_t err = rd.err;
+    // ---- the status, the builder and the item lists, derived alike in every pass
+    uint32_t builder = CDR_BUILDER_LOCAL;
+    cdr_repl_state rs;
+    {
+      uint64_t* z = reinterpret_cast<uint64_t*>(&rs);
+#pragma unroll
+      for (uint32_t i = 0; i < sizeof(rs) / 8; i++) z[i] = 0;
+    }
+    Tok tok{Span{0, 0}, 0, 0};
+    uint32_t n_rp = 0, n_sa = 0, n_vh = 0;
+    bool has_points = false, vh_branch = false;
+    Span points{0, 0}, items{0, 0};
+    if (!(R.has & X_PARENT)) {
+      R.pdom = R.pwf = R.prun = Span{0, 0};
+      R.x.initiated_id = CDR_EMPTY_EVENT_ID;
+    }
+    if (!err && ((R.pdom.n != 0 && R.pdom.n != 16) || (R.prun.n != 0 && R.prun.n != 16))) err = CDR_LOAD_E_UUID;
+    if (!err && (R.has & X_F44) && (R.has & X_VH)) err = CDR_LOAD_E_SHAPE;
+    if (!err && (R.has & X_F44)) {
+      builder = CDR_BUILDER_2DC;
+      rs.present = 1;
+      rs.start_version = R.ps.start_version;
+      rs.current_version = R.ps.current_version;
+      rs.last_write_version = C.in.last_write_version[w];
+      rs.last_write_event_id = R.f44;
+      if (R.lri.n >= 6 && rd.at(R.lri.at) == T_STRING && rd.at(R.lri.at + 1) == T_STRUCT) {
+        Rd q = sub_reader(rd, R.lri.at + 2, R.lri.n - 2);
+        const uint32_t cnt = (uint32_t)q.size();
+        for (uint32_t k = 0; k < cnt && q.ok() && !err; k++) {
+          Span key{0, 0};
+          f_str(q, T_STRING, &key);
+          int64_t ver = 0, last = 0;
+          fields(q, [&](uint32_t t, uint32_t id) {
+            switch (id) {
+              case 10: f_i64(q, t, &ver); break;
+              case 12: f_i64(q, t, &last); break;
+              default: skip1(q, t); break;
+            }
+          });
+          uint32_t ci = CDR_MAX_CLUSTERS;
+          for (uint32_t i = 0; i < C.in.n_clusters && ci == CDR_MAX_CLUSTERS; i++) {
+            const uint32_t s = C.in.cluster_seed[i];
+            if (s >= C.n_seeds) continue;
+            const uint64_t a = C.seed_off[s], n = C.seed_off[s + 1] - a;
+            if (n != key.n) continue;
+            bool same = true;
+            for (uint32_t j = 0; j < key.n && same; j++) same = rd.at(key.at + j) == C.seed_bytes[a + j];
+            if (same) ci = i;
+          }
+          if (ci == CDR_MAX_CLUSTERS) {
+            err = CDR_LOAD_E_CLUSTER;
+          } else {
+            rs.lri_mask |= 1u << ci;
+            rs.lri_version[ci] = ver;
+            rs.lri_last_event_id[ci] = last;
+          }
+        }
+      }
+    } else if (R.has & X_VH) {
+      builder = CDR_BUILDER_NDC;
+    }
+    if (!err && (R.has & X_TOKEN)) err = parse_token(rd, R.token, &tok);
+    if (!err && R.rpb.n) {  // ResetPoints{10 Points}
+      if (!is_thriftrw(rd, R.rpenc) || rd.at(R.rpb.at) != 0x59u) {
+        err = CDR_LOAD_E_ENCODING;
+      } else {
+        Rd q = sub_reader(rd, R.rpb.at + 1, R.rpb.n - 1);
+        uint32_t et = 0, cnt = 0;
+        fields(q, [&](uint32_t t, uint32_t id) {
+          if (id == 10) f_list(q, t, &et, &cnt, &points);
+          else skip1(q, t);
+        });
+        err = q.err;
+        has_points = points.n != 0 && et == T_STRUCT;
+        n_rp = has_points ? cnt : 0u;
+        if (!err && n_rp > CDR_LOAD_MAX_RESET_POINTS) err = CDR_LOAD_E_SHAPE;
+      }
+    }
+    if (!err && (R.has & X_SA)) {
+      if (rd.at(R.sam.at) == T_STRING && rd.at(R.sam.at + 1) == T_STRING) {
+        Rd q = sub_reader(rd, R.sam.at + 2, 4);
+        n_sa = (uint32_t)q.size();
+      }
+      if (n_sa > CDR_LOAD_MAX_SEARCH_ATTR) err = CDR_LOAD_E_SHAPE;
+    }
+    if (!err && (R.has & X_VH)) {  // VersionHistories{10 index, 20 [VersionHistory{10 token, 20 items}]}
+      if (!is_thriftrw(rd, R.vhenc) || R.vhb.n == 0 || rd.at(R.vhb.at) != 0x59u) {
+        err = CDR_LOAD_E_ENCODING;
+      } else {
+        Rd q = sub_reader(rd, R.vhb.at + 1, R.vhb.n - 1);
+        int32_t index = 0;
+        uint32_t et = 0, cnt = 0;
+        Span hs{0, 0};
+        fields(q, [&](uint32_t t, uint32_t id) {
+          if (id == 10) f_i32(q, t, &index);
+          else if (id == 20) f_list(q, t, &et, &cnt, &hs);
+          else skip1(q, t);
+        });
+        err = q.err;
+        if (!err && (index != 0 || hs.n == 0 || et != T_STRUCT || cnt != 1)) err = CDR_LOAD_E_SHAPE;
+        if (!err) {
+          Rd h = sub_reader(rd, hs.at + 5, hs.n - 5);
+          Span vt{0, 0};
+          uint32_t it = 0, ic = 0;
+          fields(h, [&](uint32_t t, uint32_t id) {
+            if (id == 10) f_str(h, t, &vt);
+            else if (id == 20) f_list(h, t, &it, &ic, &items);
+            else skip1(h, t);
+          });
+          if (vt.n) {
+            err = parse_token(rd, vt, &tok);
+            if (!err && (R.has & X_TOKEN)) err = CDR_LOAD_E_SHAPE;
+            vh_branch = true;
+          }
+          n_vh = (items.n != 0 && it == T_STRUCT) ? ic : 0u;
+          if (!err && n_vh > CDR_LOAD_MAX_VH_ITEMS) err = CDR_LOAD_E_SHAPE;
+        }
+      }
+    }
+    if (P == COUNT) {
+      C.status[w] = err;
+      if (err != CDR_DEC_OK) atomicMin(&C.fail[w], fail_word(CDR_LOAD_TABLES, 0, err));
+    }
+    XCnt need{{0, 0, 0, 0}};
+    if (err == CDR_DEC_OK) {
+      const XCnt o0 = P == COUNT ? XCnt{{0, 0, 0, 0}} : C.off[w];
+      const XCnt o1 = P == COUNT ? XCnt{{n_vh, n_rp, n_sa, ~0ull}} : C.off[w + 1];
+      uint64_t g = o0.v[3];  // the entry's share of gen_bytes: [g, o1.v[3])
+      auto H = [&](Span s) -> uint32_t {  // a handle field by pass: counted, interned, or looked up
+        if (s.n == 0) return 0u;
+        if (P == COUNT) {
+          n_str++;
+          return 0u;
+        }
+        const uint64_t h = rd.hash(s.at, s.n);
+        if (P == INTERN) {
+          tab_insert(C.T, h, s.at, s.n, UNASSIGNED);
+          return 0u;
+        }
+        return tab_lookup(C.T, h);
+      };
+      auto G = [&](U16 u) -> uint32_t {  // a UUID's text: generated, then as H
+        if (P == COUNT) {
+          n_str++;
+          need.v[3] += GEN_BYTES;
+          return 0u;
+        }
+        const uint64_t h = u16_hash(u);
+        if (P == INTERN) {
+          if (g + GEN_BYTES <= o1.v[3]) {
+            uint32_t* t = reinterpret_cast<uint32_t*>(C.gen + g);
+            for (uint32_t i = 0; i < GEN_BYTES; i += 4)
+              t[i >> 2] = u16_char(u, i) | (u16_char(u, i + 1) << 8) | (u16_char(u, i + 2) << 16) |
+                          (u16_char(u, i + 3) << 24);
+            tab_insert(C.T, h, (C.gen_base + g) | GEN_REF, GEN_BYTES, UNASSIGNED);
+          }
+          g += GEN_BYTES;
+          return 0u;
+        }
+        return tab_lookup(C.T, h);
+      };
+      cdr_exec_info& x = R.x;
+      x.domain_id = G(u16_col(C.in.domain_id + 16ull * w));
+      x.run_id = G(u16_col(C.in.run_id + 16ull * w));
+      {
+        const uint64_t e2 = umin64(C.in.workflow_id_off[w + 1], C.total), p2 = umin64(C.in.workflow_id_off[w], e2);
+        x.workflow_id = H(Span{p2, (uint32_t)(e2 - p2)});
+      }
+      x.parent_domain_id = R.pdom.n ? G(u16_at(rd, R.pdom.at)) : 0u;
+      x.parent_run_id = R.prun.n ? G(u16_at(rd, R.prun.at)) : 0u;
+      x.parent_workflow_id = H(R.pwf);
+      x.create_request_id = H(R.crq);
+      x.task_list = H(R.tl);
+      x.workflow_type = H(R.wt);
+      x.cron_schedule = H(R.cron);
+      x.nonretriable = H(R.nonret);
+      x.branch_tree_id = H(tok.tree);
+      x.decision_request_id = H(R.drq);
+      if (R.has & X_MEMO) {
+        const uint64_t n = (uint64_t)R.memo.n + 4;
+        if (P == COUNT) {
+          n_str++;
+          need.v[3] += n;
+        } else if (P == INTERN) {
+          if (g + n <= o1.v[3]) {
+            const uint64_t h = memo_hash(rd, R.memo, C.gen + g);
+            tab_insert(C.T, h, (C.gen_base + g) | GEN_REF, (uint32_t)n, UNASSIGNED);
+          }
+          g += n;
+        } else {
+          x.memo = tab_lookup(C.T, memo_hash(rd, R.memo, nullptr));
+        }
+      }
+      cdr_exec_persist& ps = R.ps;
+      ps.execution_context = H(R.ctx);
+      ps.sticky_task_list = H(R.stl);
+      ps.client_library_version = H(R.clv);
+      ps.client_feature_version = H(R.cfv);
+      ps.client_impl = H(R.cimpl);
+      // reset points: every pass walks them for their strings
+      {
+        const uint64_t cap = umin64(n_rp, o1.v[1] - o0.v[1]);
+        Rd q = sub_reader(rd, points.at + 5, points.n >= 5 ? points.n - 5 : 0);
+        for (uint64_t k = 0; k < cap && q.ok(); k++) {
+          cdr_reset_point pt;
+          pt.binary_checksum = pt.run_id = 0;
+          pt.first_decision_completed_id = pt.created_time_nano = pt.expiring_time_nano = 0;
+          pt.flags = pt._pad = 0;
+          Span cs{0, 0}, ru{0, 0};
+          fields(q, [&](uint32_t t, uint32_t id) {
+            const uint32_t bit = id == 10   ? CDR_RP_HAS_CHECKSUM
+                                 : id == 20 ? CDR_RP_HAS_RUN_ID
+                                 : id == 30 ? CDR_RP_HAS_FIRST_DC_ID
+                                 : id == 40 ? CDR_RP_HAS_CREATED
+                                 : id == 50 ? CDR_RP_HAS_EXPIRING
+                                 : id == 60 ? CDR_RP_HAS_RESETTABLE
+                                            : 0u;
+            const uint32_t want = id <= 20 ? T_STRING : id == 60 ? T_BOOL : T_I64;
+            if (bit && t == want) pt.flags |= bit;
+            switch (id) {
+              case 10: f_str(q, t, &cs); break;
+              case 20: f_str(q, t, &ru); break;
+              case 30: f_i64(q, t, &pt.first_decision_completed_id); break;
+              case 40: f_i64(q, t, &pt.created_time_nano); break;
+              case 50: f_i64(q, t, &pt.expiring_time_nano); break;
+              case 60: f_bool(q, t, &pt.flags, CDR_RP_RESETTABLE); break;
+              default: skip1(q, t); break;
+            }
+          });
+          pt.binary_checksum = H(cs);
+          pt.run_id = H(ru);
+          if (P == FILL) store_whole(C.rp + o0.v[1] + k, pt);
+        }
+      }
+      // search attributes, in wire order; a repeated key keeps its first slot and its last value
+      uint32_t n_keys = 0;
+      {
+        const uint64_t cap = umin64(n_sa, o1.v[2] - o0.v[2]);
+        Rd q = sub_reader(rd, R.sam.at + 6, R.sam.n >= 6 ? R.sam.n - 6 : 0);
+        cdr_kv* o = P == FILL ? C.sa + o0.v[2] : nullptr;
+        for (uint64_t k = 0; k < cap && q.ok(); k++) {
+          Span ks{0, 0}, vs{0, 0};
+          f_str(q, T_STRING, &ks);
+          f_str(q, T_STRING, &vs);
+          const uint32_t hk = H(ks), hv = H(vs);
+          if (P == FILL) {
+            uint32_t j = 0;
+            while (j < n_keys && o[j].key != hk) j++;
+            o[j] = cdr_kv{hk, hv};
+            n_keys += j == n_keys ? 1u : 0u;
+          }
+        }
+      }
+      if (P == COUNT) {
+        need.v[0] = n_vh;
+        need.v[1] = n_rp;
+        need.v[2] = n_sa;
+        need.v[3] = (need.v[3] + 3) & ~3ull;
+      }
+      if (P == FILL) {
+        const uint64_t cap = umin64(n_vh, o1.v[0] - o0.v[0]);
+        Rd q = sub_reader(rd, items.at + 5, items.n >= 5 ? items.n - 5 : 0);
+        for (uint64_t k = 0; k < cap && q.ok(); k++) {
+          cdr_vh_item it{0, 0};
+          fields(q, [&](uint32_t t, uint32_t id) {
+            if (id == 10) f_i64(q, t, &it.event_id);
+            else if (id == 20) f_i64(q, t, &it.version);
+            else skip1(q, t);
+          });
+          store_whole(C.vh + o0.v[0] + k, it);
+        }
+        x.branch_id_lo = tok.lo;
+        x.branch_id_hi = tok.hi;
+        x.attempt = (int32_t)(uint32_t)(uint64_t)R.f82;
+        x.signal_count = (int32_t)(uint32_t)(uint64_t)R.f106;
+        if (!(R.has & X_F18)) x.completion_event_batch_id = CDR_EMPTY_EVENT_ID;
+        x.next_event_id = C.in.next_event_id[w];
+        x.last_event_task_id = 0;
+        x.flags |= CDR_XI_STARTED | ((R.has & X_TOKEN) ? CDR_XI_HAS_BRANCH : 0u) |
+                   ((R.has & X_MEMO) ? CDR_XI_HAS_MEMO : 0u) | ((R.has & X_SA) ? CDR_XI_HAS_SEARCH_ATTR : 0u) |
+                   (has_points ? CDR_XI_HAS_RESET_POINTS : 0u) | (vh_branch ? CDR_XI_VH_BRANCH : 0u);
+        if (R.f94 != CDR_ZERO_TIME_NANOS) {
+          x.flags |= CDR_XI_HAS_EXPIRATION;
+          x.expiration_time = R.f94;
+        }
+        x.reset_points_len = (uint32_t)umin64(n_rp, o1.v[1] - o0.v[1]);
+        x.search_attr_len = n_keys;
+        ps.sticky_s2s_timeout = (int64_t)(int32_t)(uint32_t)(uint64_t)R.f80;
+        store_whole(C.exec + w, x);  // two 128-B halves, each whole
+        store_whole(C.repl + w, rs);
+        store_whole(C.persist + w, ps);
+        C.builder[w] = builder;
+        C.n_sa[w] = n_keys;
+      }
+    }
+    if (P == COUNT) C.cnt[w] = need;
+  }
+  if (P == COUNT) {
+    for (int o = 32; o > 0; o >>= 1) n_str += __shfl_down(n_str, o, 64);
+    if (lane == 0 && n_str) atomicAdd(C.totals, (unsigned long long)n_str);
+  }
+}
+
 // the entry of each row: the last w with entry_row0[w] <= r (empty entries share a start)
 __global__ void k_row_entry(const uint32_t* row0, uint32_t n_entries, uint32_t n_rows, uint32_t* row_entry) {
   const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -473,7 +1057,8 @@ struct EpiIn {
   uint32_t n_rows[CDR_LOAD_TABLES];
 };
 __global__ void k_epilogue(EpiIn E, uint32_t n_entries, const unsigned long long* fail, cdr_wf_result* result,
-                           cdr_wf_caps* caps, int32_t* entry_status, uint32_t* n_bad) {
+                           cdr_wf_caps* caps, int32_t* entry_status, uint32_t* n_bad, const XCnt* xoff,
+                           const uint32_t* n_sa) {
   const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
   if (w >= n_entries) return;
   unsigned long long f = fail[w];
@@ -508,6 +1093,15 @@ __global__ void k_epilogue(EpiIn E, uint32_t n_entries, const unsigned long long
   }
   c.act_off = off[0], c.timer_off = off[1], c.child_off = off[2], c.cancel_off = off[3], c.signal_off = off[4];
   c.act_cap = cnt[0], c.timer_cap = cnt[1], c.child_cap = cnt[2], c.cancel_cap = cnt[3], c.signal_cap = cnt[4];
+  if (xoff) {  // the execution row's item tables (cdr_load_state)
+    const XCnt a = xoff[w], b = xoff[w + 1];
+    c.vh_off = a.v[0], c.rp_off = a.v[1], c.sa_off = a.v[2];
+    c.vh_cap = (uint32_t)(b.v[0] - a.v[0]), c.rp_cap = (uint32_t)(b.v[1] - a.v[1]);
+    c.sa_cap = (uint32_t)(b.v[2] - a.v[2]);
+    res.n_vh = ok ? c.vh_cap : 0u;
+    res.n_reset_points = ok ? c.rp_cap : 0u;
+    res.n_search_attr = ok ? n_sa[w] : 0u;
+  }
   result[w] = res;
   caps[w] = c;
   entry_status[w] = ok ? CDR_DEC_OK : (int32_t)(f & 0xFFu);
@@ -555,10 +1149,21 @@ void launch_rows(int t, const LCtx& C, hipStream_t st) {
   }
 }
 
-}  // namespace
+template <int P>
+void launch_exec(const XCtx& X, hipStream_t st) {
+  if (!X.n_entries) return;
+  const dim3 grid((X.n_entries + CDR_LOAD_BLOCK - 1) / CDR_LOAD_BLOCK), blk(CDR_LOAD_BLOCK);
+  hipLaunchKernelGGL((k_exec<P>), grid, blk, (CDR_LOAD_BLOCK / 64) * CDR_LOAD_STAGE, st, X);
+}
 
-extern "C" int cdr_load_rows(cdr_ctx* ctx, const cdr_rows_in* in, cdr_rows_out* out, void* stream) {
+// cdr_load_rows (xin == NULL) and cdr_load_state
+int load_impl(cdr_ctx* ctx, const cdr_rows_in* in, const cdr_exec_rows_in* xin, cdr_rows_out* out,
+              cdr_state_out* xout, void* stream) {
   if (!ctx || !in || !out || !in->seed_off || in->n_seeds == 0) return CDR_API_EINVAL;
+  if (xin && in->n_entries &&
+      (!xin->blob_off || !xin->domain_id || !xin->run_id || !xin->workflow_id_off || !xin->next_event_id ||
+       !xin->last_write_version || xin->n_clusters > CDR_MAX_CLUSTERS || (in->n_bytes && !in->bytes)))
+    return CDR_API_EINVAL;
   constexpr int NT = CDR_LOAD_TABLES;
   uint64_t n_all = 0, base[NT + 1];
   for (int t = 0; t < NT; t++) {
@@ -605,9 +1210,30 @@ extern "C" int cdr_load_rows(cdr_ctx* ctx, const cdr_rows_in* in, cdr_rows_out* 
       (rc = ws(ctx, WS_LD_DEST, n_all + 1, &dest)) || (rc = ws(ctx, WS_LD_TKEY, in->n_rows[1] + 1ull, &tkey)) ||
       (rc = ws(ctx, WS_LD_FAIL, 2ull * ne + 1, &fail)) || (rc = ws(ctx, WS_LD_ESTATUS, ne + 1ull, &estatus)) ||
       (rc = ws(ctx, WS_LD_RESULT, ne + 1ull, &result)) || (rc = ws(ctx, WS_LD_CAPS, ne + 1ull, &caps)) ||
-      (rc = ws(ctx, WS_LD_GEN, (uint64_t)GEN_BYTES * in->n_rows[2] + 8, &gen)) ||
       (rc = ws(ctx, WS_LD_MISC, 16, &misc)))
     return rc;
+  XCtx X{};
+  XCnt* xoff = nullptr;
+  uint32_t* n_sa = nullptr;
+  const bool with_exec = xin && ne;
+  if (with_exec) {
+    X.bytes = in->bytes;
+    X.total = in->n_bytes;
+    X.in = *xin;
+    X.seed_bytes = in->seed_bytes;
+    X.seed_off = in->seed_off;
+    X.n_seeds = in->n_seeds;
+    X.n_entries = ne;
+    if ((rc = ws(ctx, WS_LD_XSTATUS, ne + 1ull, &X.status)) || (rc = ws(ctx, WS_LD_XCNT, ne + 1ull, &X.cnt)) ||
+        (rc = ws(ctx, WS_LD_XOFF, ne + 1ull, &xoff)) || (rc = ws(ctx, WS_LD_EXEC, ne + 1ull, &X.exec)) ||
+        (rc = ws(ctx, WS_LD_REPL, ne + 1ull, &X.repl)) || (rc = ws(ctx, WS_LD_PERSIST, ne + 1ull, &X.persist)) ||
+        (rc = ws(ctx, WS_LD_BUILDER, ne + 1ull, &X.builder)) || (rc = ws(ctx, WS_LD_NSA, ne + 1ull, &n_sa)))
+      return rc;
+    X.off = xoff;
+    X.n_sa = n_sa;
+    X.fail = fail;
+    HIPCHK(hipMemsetAsync(X.cnt + ne, 0, sizeof(XCnt), st));
+  }
   for (int t = 0; t < NT; t++) {
     recs[t] = cdr_ws_get(ctx, rec_slot[t], (in->n_rows[t] + 1ull) * rec_size[t]);
     if (!recs[t]) return CDR_API_ENOMEM;
@@ -635,7 +1261,6 @@ extern "C" int cdr_load_rows(cdr_ctx* ctx, const cdr_rows_in* in, cdr_rows_out* 
     c.fail = fail;
     c.status = status + base[t];
     c.totals = n_fields;
-    c.gen = gen;
     c.dest = dest + base[t];
     c.recs = recs[t];
     c.tkey = tkey;
@@ -647,11 +1272,32 @@ extern "C" int cdr_load_rows(cdr_ctx* ctx, const cdr_rows_in* in, cdr_rows_out* 
   HIPCHK(hipGetLastError());
   // ---- pass 1: statuses and string-field counts
   for (int t = 0; t < NT; t++) launch_rows<COUNT>(t, C[t], st);
+  XCnt xtot{{0, 0, 0, 0}};
+  if (with_exec) {  // ... and the execution rows' item counts and gen_bytes need, scanned into offsets
+    X.totals = n_fields;
+    launch_exec<COUNT>(X, st);
+    size_t tb = 0;
+    HIPCHK(hipcub::DeviceScan::ExclusiveScan(nullptr, tb, X.cnt, xoff, XCntAdd(), XCnt{{0, 0, 0, 0}}, (int)(ne + 1), st));
+    void* tmp = cdr_ws_get(ctx, WS_LD_XTMP, tb ? tb : 8);
+    if (!tmp) return CDR_API_ENOMEM;
+    HIPCHK(hipcub::DeviceScan::ExclusiveScan(tmp, tb, X.cnt, xoff, XCntAdd(), XCnt{{0, 0, 0, 0}}, (int)(ne + 1), st));
+    HIPCHK(hipMemcpyAsync(&xtot, xoff + ne, sizeof(XCnt), hipMemcpyDeviceToHost, st));
+  }
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(ctx->ld_ev[1], st));
   uint64_t n_str_fields = 0;
   HIPCHK(hipMemcpyAsync(&n_str_fields, n_fields, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
+  const uint64_t gen_rows = (uint64_t)GEN_BYTES * in->n_rows[2];  // the child rows' part of gen_bytes
+  if ((rc = ws(ctx, WS_LD_GEN, gen_rows + xtot.v[3] + 8, &gen))) return rc;
+  for (int t = 0; t < NT; t++) C[t].gen = gen;
+  if (with_exec) {
+    X.gen = gen + gen_rows;
+    X.gen_base = gen_rows;
+    if ((rc = ws(ctx, WS_LD_VH, xtot.v[0] + 1, &X.vh)) || (rc = ws(ctx, WS_LD_RP, xtot.v[1] + 1, &X.rp)) ||
+        (rc = ws(ctx, WS_LD_SA, xtot.v[2] + 1, &X.sa)))
+      return rc;
+  }
   uint64_t cap = 1024;
   while (cap < 2 * (n_str_fields + in->n_seeds)) cap <<= 1;
   STab T{};
@@ -666,6 +1312,10 @@ extern "C" int cdr_load_rows(cdr_ctx* ctx, const cdr_rows_in* in, cdr_rows_out* 
   for (int t = 0; t < NT; t++) {
     C[t].T = T;
     launch_rows<INTERN>(t, C[t], st);
+  }
+  if (with_exec) {
+    X.T = T;
+    launch_exec<INTERN>(X, st);
   }
   if (in->n_rows[2])
     hipLaunchKernelGGL(k_gen_intern, grid(in->n_rows[2]), blk, 0, st, T, gen, row_entry + base[2], fail,
@@ -729,7 +1379,10 @@ extern "C" int cdr_load_rows(cdr_ctx* ctx, const cdr_rows_in* in, cdr_rows_out* 
     E.row0[t] = in->entry_row0[t];
     E.n_rows[t] = in->n_rows[t];
   }
-  if (ne) hipLaunchKernelGGL(k_epilogue, grid(ne), blk, 0, st, E, ne, fail, result, caps, estatus, misc + 2);
+  if (with_exec) launch_exec<FILL>(X, st);
+  if (ne)
+    hipLaunchKernelGGL(k_epilogue, grid(ne), blk, 0, st, E, ne, fail, result, caps, estatus, misc + 2,
+                       (const XCnt*)(with_exec ? xoff : nullptr), (const uint32_t*)n_sa);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(ctx->ld_ev[4], st));
   uint32_t n_bad = 0;
@@ -751,9 +1404,35 @@ extern "C" int cdr_load_rows(cdr_ctx* ctx, const cdr_rows_in* in, cdr_rows_out* 
   for (int t = 0; t < NT; t++) out->row_status[t] = status + base[t];
   out->entry_status = estatus;
   out->gen_bytes = gen;
-  out->n_gen_bytes = (uint64_t)GEN_BYTES * in->n_rows[2];
+  out->n_gen_bytes = gen_rows + xtot.v[3];
   out->n_bad_entries = n_bad;
+  if (with_exec) {
+    out->state.exec = X.exec;
+    out->state.repl = X.repl;
+    out->state.vh = X.vh;
+    out->state.rp = X.rp;
+    out->state.sa = X.sa;
+    out->totals.vh = xtot.v[0];
+    out->totals.rp = xtot.v[1];
+    out->totals.sa = xtot.v[2];
+    xout->persist = X.persist;
+    xout->builder = X.builder;
+    xout->exec_status = X.status;
+  }
   return CDR_API_OK;
+}
+
+}  // namespace
+
+extern "C" int cdr_load_rows(cdr_ctx* ctx, const cdr_rows_in* in, cdr_rows_out* out, void* stream) {
+  return load_impl(ctx, in, nullptr, out, nullptr, stream);
+}
+
+extern "C" int cdr_load_state(cdr_ctx* ctx, const cdr_rows_in* rows, const cdr_exec_rows_in* exec,
+                              cdr_state_out* out, void* stream) {
+  if (!out) return CDR_API_EINVAL;
+  *out = cdr_state_out{};
+  return load_impl(ctx, rows, exec, &out->rows, out, stream);
 }
 
 extern "C" int cdr_load_pass_ms(cdr_ctx* ctx, float* ms) {

@@ -1,11 +1,14 @@
 """Host side of the persisted-row loader (cdr.h cdr_load_rows, csrc/load.hip).
 
 ``encode_state`` runs the existing row encoders over the five pending tables of replayed
-states and packs their blobs the way a store would hand them back (a ``Rows``, the host
-form of cdr_rows_in); ``load`` decodes a ``Rows`` on the device and returns host copies
-of every output; ``to_carry`` turns a decode plus the caller's exec / repl / vh / rp / sa
-records (the execution row is not decoded: cdr.h) into an ``engine.Carry`` a batch can
-replay onto.  ``gather`` runs cdr_strtab_gather_async on any decoded string table.
+states — and, with ``exec_rows=True``, over their execution rows — and packs the blobs the
+way a store would hand them back (a ``Rows``, the host form of cdr_rows_in and
+cdr_exec_rows_in); ``load`` decodes the pending tables of a ``Rows`` on the device
+(cdr_load_rows) and ``load_state`` the execution rows with them (cdr_load_state), both
+returning host copies of every output; ``to_carry`` turns a decode into an ``engine.Carry``
+a batch can replay onto — a ``load_state`` result as it is, a ``load`` result with the
+caller's exec / repl / vh / rp / sa records.  ``gather`` runs cdr_strtab_gather_async on
+any decoded string table.
 """
 from __future__ import annotations
 
@@ -27,6 +30,19 @@ HANDLES = {"act": ("activity_id", "request_id", "task_list", "nonretriable"), "t
 
 
 @dataclasses.dataclass
+class ExecRows:
+    """cdr_exec_rows_in on the host: entry w's execution row is bytes[blob_off[w]:blob_off[w+1]]
+    of the Rows that holds it, its workflow ID bytes[workflow_id_off[w]:workflow_id_off[w+1]]."""
+    blob_off: np.ndarray            # uint64 [n_entries + 1]
+    domain_id: np.ndarray           # uint8 [16 * n_entries]
+    run_id: np.ndarray              # uint8 [16 * n_entries]
+    workflow_id_off: np.ndarray     # uint64 [n_entries + 1]
+    next_event_id: np.ndarray       # int64 [n_entries]
+    last_write_version: np.ndarray  # int64 [n_entries]
+    cluster_seed: list              # seed index of cluster i's name
+
+
+@dataclasses.dataclass
 class Rows:
     """cdr_rows_in on the host.  Row r of table t: blob bytes[blob_off[t][r]:blob_off[t][r+1]],
     key[t][r] (tables 0, 2-4) or the timer ID bytes[timer_id_off[r]:timer_id_off[r+1]]
@@ -39,6 +55,7 @@ class Rows:
     act_heartbeat: np.ndarray  # int64 [n_rows[0]]
     n_entries: int
     src: list = None           # encode_state: 5 x [(entry, row j of the entry)] per packed row
+    exec: ExecRows = None      # the execution rows (cdr_load_state)
 
     @property
     def n_rows(self):
@@ -51,11 +68,13 @@ class Rows:
         return self.bytes[int(self.timer_id_off[r]):int(self.timer_id_off[r + 1])].tobytes()
 
 
-def pack(n_entries: int, tables) -> Rows:
+def pack(n_entries: int, tables, exec_rows=None, cluster_seed=()) -> Rows:
     """tables[t][w] = entry w's rows of table t in arrival order: (key, blob) for tables 0,
     2, 3, 4 — table 0 may add a third item, the heartbeat column (default: Go's zero time) —
     and (timer ID bytes, blob) for table 1.  Each table's blobs are contiguous in `bytes`,
-    the timer IDs follow the last blob."""
+    the timer IDs follow the last blob.  exec_rows[w] = (blob, domain ID's 16 bytes, run ID's
+    16 bytes, workflow ID, next_event_id, last_write_version) adds the execution rows: the
+    workflow IDs follow the timer IDs and the execution blobs come last."""
     chunks, pos = [], 0
     offs, row0, keys, hb, ids = [], [], [], [], []
     for t in range(5):
@@ -80,8 +99,26 @@ def pack(n_entries: int, tables) -> Rows:
         chunks.append(s)
         pos += len(s)
         tid_off.append(pos)
+    xr = None
+    if exec_rows is not None:
+        assert len(exec_rows) == n_entries and all(len(x[1]) == 16 and len(x[2]) == 16 for x in exec_rows)
+        wid_off = [pos]
+        for x in exec_rows:
+            chunks.append(bytes(x[3]))
+            pos += len(x[3])
+            wid_off.append(pos)
+        xoff = [pos]
+        for x in exec_rows:
+            chunks.append(bytes(x[0]))
+            pos += len(x[0])
+            xoff.append(pos)
+        xr = ExecRows(np.array(xoff, np.uint64), np.frombuffer(b"".join(bytes(x[1]) for x in exec_rows), np.uint8).copy(),
+                      np.frombuffer(b"".join(bytes(x[2]) for x in exec_rows), np.uint8).copy(),
+                      np.array(wid_off, np.uint64), np.array([x[4] for x in exec_rows], np.int64),
+                      np.array([x[5] for x in exec_rows], np.int64), list(cluster_seed))
     data = np.frombuffer(b"".join(chunks) or b"\0", np.uint8).copy()
-    return Rows(data[:pos], offs, row0, keys, np.array(tid_off, np.uint64), np.array(hb, np.int64), n_entries)
+    return Rows(data[:pos], offs, row0, keys, np.array(tid_off, np.uint64), np.array(hb, np.int64), n_entries,
+                exec=xr)
 
 
 def heartbeat_column(a) -> int:
@@ -121,12 +158,71 @@ def state_strings(batch: engine.Batch, out: engine.Outputs, strings=None) -> lis
     return tab
 
 
-def encode_state(eng: engine.Engine, batch: engine.Batch, out: engine.Outputs, strings: list) -> Rows:
+X_HANDLES = ("domain_id", "workflow_id", "run_id", "create_request_id", "parent_domain_id", "parent_workflow_id",
+             "parent_run_id", "task_list", "workflow_type", "cron_schedule", "memo", "nonretriable", "branch_tree_id",
+             "decision_request_id")
+X_UUIDS = ("domain_id", "run_id", "parent_domain_id", "parent_run_id")
+ITEM_HANDLES = {"rp": ("binary_checksum", "run_id"), "sa": ("key", "value")}
+
+
+def whole_state_strings(batch: engine.Batch, out: engine.Outputs, extra: int = 0, strings=None) -> list:
+    """state_strings extended to the execution rows: a table of distinct strings covering every
+    handle the OK entries of `out` name anywhere (and `extra` more handles after them, for a
+    persistence context or cluster names), with canonical UUID text for the handles used as a
+    domain, run or parent ID, a Memo struct body for Memo handles and a list<string> body for
+    RetryNonRetryableErrors handles."""
+    hmax, uuids, memos, lists = 1, set(), set(), set()
+    for w in range(batch.n_wfs):
+        if out.result[w].code != abi.OK:
+            continue
+        x = out.exec[w]
+        hmax = max([hmax] + [getattr(x, f) for f in X_HANDLES])
+        uuids |= {getattr(x, f) for f in X_UUIDS}
+        memos.add(x.memo)
+        lists.add(x.nonretriable)
+        for t in TABLES + ("rp", "sa"):
+            for r in out.rows(w, t):
+                hmax = max([hmax] + [getattr(r, f) for f in {**HANDLES, **ITEM_HANDLES}[t]])
+                if t == "child":
+                    uuids.add(r.started_run_id)
+                if t == "act":
+                    lists.add(r.nonretriable)
+    tab = [b""] + [stand_in(h, strings) for h in range(1, hmax + 1 + extra)]
+    for h in lists - {0}:
+        s = stand_in(h, strings)
+        tab[h] = struct.pack(">bi", 11, 1) + struct.pack(">i", len(s)) + s
+    for h in memos - {0}:
+        k = b"memo-%d" % h
+        tab[h] = b"\x0d\x00\x0a" + struct.pack(">bbi", 11, 11, 1) + struct.pack(">i", len(k)) + k + \
+            struct.pack(">i", 2) + b"mv" + b"\x00"
+    for h in uuids - {0}:
+        tab[h] = run_id_text(h)
+    return tab
+
+
+def uuid_bytes(text: bytes) -> bytes:
+    """The 16 bytes of a key column from an ID's text (sqldb.MustParseUUID); an ID that is no
+    UUID — a row the store could not hold — becomes its first 16 bytes, zero-padded."""
+    h = bytes(text).replace(b"-", b"")
+    try:
+        if len(h) == 32:
+            return bytes.fromhex(h.decode("ascii"))
+    except (ValueError, UnicodeDecodeError):
+        pass
+    return bytes(text)[:16].ljust(16, b"\0")
+
+
+def encode_state(eng: engine.Engine, batch: engine.Batch, out: engine.Outputs, strings: list, exec_rows: bool = False,
+                 persist=None, cluster_names=None) -> Rows:
     """The five pending tables of the OK entries of `out` as the SQL persistence stores
     them: the device encoders' blobs (cdr_encode_blobs_async / cdr_encode_rows_async), the
     key columns and the activity heartbeat column from the records, timer IDs from
     `strings`.  A row an encoder refuses (status != 0) is left out of its entry.
-    `.src[t]` names each packed row's (entry, row of the entry)."""
+    `.src[t]` names each packed row's (entry, row of the entry).
+    exec_rows=True adds the execution rows: cdr_encode_blobs_async table 5 with `persist` (a
+    cdr_exec_persist array; default: zeros but a 2DC entry's start / current version) and `cluster_names` (handles), the key columns from
+    the exec records' strings, next_event_id and last_write_version from the records; an entry
+    that is not OK, or whose row the encoder refuses, gets an empty blob (it fails to load)."""
     blobs = {}
     for t in TABLES:
         if t in ("timer", "cancel"):
@@ -156,7 +252,24 @@ def encode_state(eng: engine.Engine, batch: engine.Batch, out: engine.Outputs, s
             per_entry.append(rows)
         tables.append(per_entry)
         src.append(s)
-    rows = pack(batch.n_wfs, tables)
+    xrows = None
+    if exec_rows:
+        names = list(cluster_names if cluster_names is not None else [])
+        if persist is None:  # buildExecutionRow's start / current version are the replication state's
+            persist = (abi.CdrExecPersist * max(1, batch.n_wfs))()
+            for w in range(batch.n_wfs):
+                if batch.wfs[w].builder == abi.BUILDER_2DC:
+                    persist[w].start_version = out.repl[w].start_version
+                    persist[w].current_version = out.repl[w].current_version
+        got, codes = eng.encode_blobs(batch, out, "exec", strings, persist, names)
+        S = lambda h: strings[h] if h < len(strings) else b""  # noqa: E731
+        xrows = []
+        for w in range(batch.n_wfs):
+            x = out.exec[w]
+            blob = got[w] if w in got and codes[w] == 0 else b""
+            xrows.append((blob, uuid_bytes(S(x.domain_id)), uuid_bytes(S(x.run_id)), S(x.workflow_id), x.next_event_id,
+                          out.repl[w].last_write_version))
+    rows = pack(batch.n_wfs, tables, xrows, cluster_names or ())
     rows.src = src
     return rows
 
@@ -176,6 +289,12 @@ class Loaded:
     n_bad_entries: int
     gathered: list = None     # load(gather=True): the table cdr_strtab_gather_async built
     rc: int = 0
+    # load_state with execution rows: the records per entry (tables also holds "vh", "rp", "sa")
+    exec: C.Array = None
+    repl: C.Array = None
+    persist: C.Array = None
+    builder: np.ndarray = None      # uint32 [n_entries]
+    exec_status: np.ndarray = None  # int32 [n_entries]
 
     def rows(self, w: int, t: str):
         off = getattr(self.caps[w], t + "_off")
@@ -251,6 +370,18 @@ def load(eng: engine.Engine, rows: Rows, seeds: list, at_end: bool = False, gath
     uploaded so that it ends where its allocation ends.  `gather`: also build the
     contiguous string table on the device (cdr_strtab_gather_async) -> .gathered.
     check=False returns the call's status in .rc instead of raising."""
+    return _load(eng, rows, seeds, at_end, gather, check, False)
+
+
+def load_state(eng: engine.Engine, rows: Rows, seeds: list, at_end: bool = False, gather: bool = False,
+               check: bool = True, cluster_seed=None) -> Loaded:
+    """cdr_load_state on the device: as `load`, with the execution rows of `rows.exec` decoded
+    too (rows.exec None: exec == NULL, cdr_load_rows' results).  `cluster_seed` overrides
+    rows.exec.cluster_seed: the index in `seeds` of each cluster's name."""
+    return _load(eng, rows, seeds, at_end, gather, check, True, cluster_seed)
+
+
+def _load(eng, rows, seeds, at_end, gather, check, state, cluster_seed=None) -> Loaded:
     L = abi.lib()
     dev = DeviceBuffers()
     try:
@@ -268,11 +399,26 @@ def load(eng: engine.Engine, rows: Rows, seeds: list, at_end: bool = False, gath
         inp.act_heartbeat = dev.up(rows.act_heartbeat)
         inp.seed_bytes, inp.seed_off = dev.up(sb), dev.up(so)
         inp.n_entries, inp.n_seeds = rows.n_entries, len(seeds)
-        out = abi.CdrRowsOut()
-        rc = L.cdr_load_rows(eng.ctx, C.byref(inp), C.byref(out), None)
+        X = rows.exec if state else None
+        if state:
+            sout, xin = abi.CdrStateOut(), None
+            if X is not None:
+                xin = abi.CdrExecRowsIn()
+                xin.blob_off, xin.workflow_id_off = dev.up(X.blob_off), dev.up(X.workflow_id_off)
+                xin.domain_id, xin.run_id = dev.up(X.domain_id), dev.up(X.run_id)
+                xin.next_event_id, xin.last_write_version = dev.up(X.next_event_id), dev.up(X.last_write_version)
+                cs = list(X.cluster_seed if cluster_seed is None else cluster_seed)
+                xin.n_clusters = len(cs)
+                for i, h in enumerate(cs[:abi.MAX_CLUSTERS]):
+                    xin.cluster_seed[i] = h
+            rc = L.cdr_load_state(eng.ctx, C.byref(inp), C.byref(xin) if xin is not None else None, C.byref(sout), None)
+            out = sout.rows
+        else:
+            out = abi.CdrRowsOut()
+            rc = L.cdr_load_rows(eng.ctx, C.byref(inp), C.byref(out), None)
         if rc:
             if check:
-                raise RuntimeError(f"cdr_load_rows rc={rc}")
+                raise RuntimeError(f"cdr_load_{'state' if state else 'rows'} rc={rc}")
             return Loaded({}, None, None, abi.CdrTotals(), [], np.zeros(0, np.int32), [], None, None, b"", 0, rc=rc)
         ne = rows.n_entries
 
@@ -295,6 +441,14 @@ def load(eng: engine.Engine, rows: Rows, seeds: list, at_end: bool = False, gath
             r &= abi.STR_REF_GEN - 1
             strings.append(src[r:r + n])
         res = Loaded(tables, result, caps, out.totals, status, est, strings, ref, ln, gen, out.n_bad_entries)
+        if X is not None:
+            for t in ("vh", "rp", "sa"):
+                tables[t] = recs(getattr(out.state, t), engine.TABLE_TYPES[t], getattr(out.totals, t))
+            res.exec = recs(out.state.exec, abi.CdrExecInfo, ne)
+            res.repl = recs(out.state.repl, abi.CdrReplState, ne)
+            res.persist = recs(sout.persist, abi.CdrExecPersist, ne)
+            res.builder = dev.down(sout.builder, np.uint32, ne)
+            res.exec_status = dev.down(sout.exec_status, np.int32, ne)
         if gather:
             res.gathered = _gather(eng, dev, out.str_ref, out.str_len, out.n_strings, inp.bytes, inp.seed_bytes,
                                    out.gen_bytes)
@@ -303,11 +457,31 @@ def load(eng: engine.Engine, rows: Rows, seeds: list, at_end: bool = False, gath
         dev.free()
 
 
-def to_carry(loaded: Loaded, other: engine.Outputs, src=None) -> engine.Carry:
-    """A Carry over the decoded pending tables plus the caller's exec / repl / vh / rp / sa
-    records (`other`, entry for entry: the execution row is not decoded).  src defaults to
-    every entry that loaded and whose `other` record is OK (-1: fresh builder)."""
+def to_carry(loaded: Loaded, other: engine.Outputs = None, src=None) -> engine.Carry:
+    """A Carry over a decode.  A `load_state` result with its execution rows is a whole state:
+    `other` is not needed, and src defaults to every entry that loaded (-1: fresh builder).
+    A `load` result holds the pending tables alone: the exec / repl / vh / rp / sa records come
+    from the caller (`other`, entry for entry), and src defaults to every entry that loaded
+    and whose `other` record is OK."""
     n = len(loaded.result)
+    if other is None:
+        if loaded.exec is None:
+            raise ValueError("a decode without execution rows needs the caller's records (other)")
+        caps = (abi.CdrWfCaps * max(1, n))()
+        tot = abi.CdrTotals()
+        for t in TABLES + ("vh", "rp", "sa"):
+            setattr(tot, t, getattr(loaded.totals, t))
+        st = engine.Outputs(SimpleNamespace(n_wfs=n), engine.Plan(caps, tot))
+        if n:
+            C.memmove(caps, loaded.caps, C.sizeof(abi.CdrWfCaps) * n)
+            C.memmove(st.result, loaded.result, C.sizeof(abi.CdrWfResult) * n)
+            C.memmove(st.exec, loaded.exec, C.sizeof(abi.CdrExecInfo) * n)
+            C.memmove(st.repl, loaded.repl, C.sizeof(abi.CdrReplState) * n)
+            for t in TABLES + ("vh", "rp", "sa"):
+                C.memmove(st.tables[t], loaded.tables[t], C.sizeof(loaded.tables[t]))
+        if src is None:
+            src = np.array([w if st.result[w].code == abi.OK else -1 for w in range(n)], np.int32)
+        return engine.Carry(src=np.asarray(src, np.int32), state=st)
     assert n == other.n_wfs
     caps = (abi.CdrWfCaps * max(1, n))()
     tot = abi.CdrTotals()

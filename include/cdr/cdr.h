@@ -20,6 +20,10 @@
  *   sql row blobs (timerInfoToBlob, requestCancelInfoToBlob)
  *                                       common/persistence/sql/workflowStateMaps.go:239-260,504-521
  *     -> cdr_encode_rows_async
+ *   sqlExecutionManager.GetWorkflowExecution
+ *                                       common/persistence/sql/sqlExecutionManager.go:206-332
+ *     -> cdr_load_state (stored rows -> the loaded state cdr_carry takes; cdr_load_rows: its
+ *        pending tables alone)
  *   common.WorkflowIDToHistoryShard     common/util.go:249-252
  *     -> cdr_workflow_id_to_shard (farmhash Fingerprint32 % numShards)
  *
@@ -861,9 +865,10 @@ int cdr_plan_ndc_apply(const cdr_batch* b, const cdr_wf_caps* state_caps, cdr_wf
  * getSignalInfoMap (common/persistence/sql/workflowStateMaps.go:139-206, 297-332, 423-471,
  * 561-596, 689-727), all through thriftRWDecode (blob.go:75-84).  Tables are numbered as in
  * the encoders: 0 activity, 1 timer, 2 child, 3 request-cancel, 4 signal.
- * OUT OF SCOPE: the execution row (one per workflow, nested blobs, key columns whose UUIDs
- * would need new text) — the caller keeps supplying the exec / repl / vh / rp / sa records —
- * and the Cassandra form.
+ * cdr_load_rows decodes these five tables alone (the caller supplies the exec / repl / vh / rp /
+ * sa records); cdr_load_state below decodes the execution row with them.
+ * OUT OF SCOPE of both: the Cassandra form, BufferedEvents, SignalRequestedIDs and the
+ * execution row's CompletionEvent.
  *
  * Blob format.  A blob is a bare thriftrw binary-protocol struct with no 0x59 preamble
  * (blob.go:61-84).  The wire rules are those of cdr/ingest.h: fields in any order, unknown
@@ -938,8 +943,8 @@ int cdr_plan_ndc_apply(const cdr_batch* b, const cdr_wf_caps* state_caps, cdr_wf
  * clamped: no byte outside [bytes, bytes + n_bytes) is read.
  *
  * Outputs live in the context's grow-only workspace (slots of their own: a later
- * cdr_ingest_decode does not touch them) and stay valid until the next cdr_load_rows on the
- * context: `state` is a cdr_out view with the five pending tables ([n_rows[t]] records) and
+ * cdr_ingest_decode does not touch them) and stay valid until the next cdr_load_rows or
+ * cdr_load_state on the context: `state` is a cdr_out view with the five pending tables ([n_rows[t]] records) and
  * result[n_entries] filled, exec / repl / vh / rp / sa and the task pointers NULL; caps[w]
  * (device) has *_off = entry_row0[t][w], *_cap = the entry's row count and everything else 0;
  * totals = the row counts.  All-empty tables and zero entries are valid.  No allocation once
@@ -976,7 +981,135 @@ typedef struct cdr_rows_out { /* device buffers owned by the context */
   uint32_t n_strings, n_bad_entries;
 } cdr_rows_out;
 int cdr_load_rows(cdr_ctx* ctx, const cdr_rows_in* in, cdr_rows_out* out, void* stream);
-/* Device milliseconds of the last cdr_load_rows on the context, between HIP events on its
+/* Whole stored states: the five pending tables as cdr_load_rows decodes them and, with them,
+ * the execution row of every entry — GetWorkflowExecution (common/persistence/sql/
+ * sqlExecutionManager.go:206-332: workflowExecutionInfoFromBlob and the row's columns) followed
+ * by DeserializeExecutionInfo / DeserializeVersionHistories (common/persistence/
+ * executionStore.go:108, 746-757), DeserializeResetPoints / DeserializeVersionHistories
+ * (serializer.go:127, 168) and NewVersionHistoriesFromThrift (versionHistory.go:366).  The
+ * result is a loaded state cdr_carry takes as it is: nothing of an earlier replay is needed.
+ * `exec` == NULL is cdr_load_rows (which is this call with exec == NULL).
+ *
+ * One string-interning pass serves the pending rows and the execution rows, so the handles of
+ * the exec record, the reset points, the search attributes and the pending rows live in one
+ * handle space (seeds first, then hash rank).  The handles of the same pending rows therefore
+ * DIFFER between cdr_load_rows and cdr_load_state with exec != NULL: more strings are ranked.
+ *
+ * Inputs (cdr_exec_rows_in, device pointers, one row per entry of rows->n_entries): the `data`
+ * column at rows->bytes[blob_off[w], blob_off[w+1]), a bare thriftrw struct as the other
+ * tables' (sqlblobs.thrift:73-134); the BINARY(16) key columns domain_id and run_id, 16 bytes
+ * per entry; the workflow ID at rows->bytes[workflow_id_off[w], workflow_id_off[w+1]); the
+ * next_event_id and last_write_version columns; cluster_seed[i] (i < n_clusters <=
+ * CDR_MAX_CLUSTERS), the seed whose bytes are cluster i's name.  Offsets are clamped to
+ * rows->n_bytes as in cdr_load_rows; the fixed-size columns are read at their entry's index.
+ *
+ * Field mapping: the inverse of the table-5 writer of cdr_encode_blobs_async (oracle/
+ * thrift_binary.py exec_info_blob restates it).  Wire rules and absent fields as for the
+ * pending tables.  cdr_exec_info:
+ *   domain_id / run_id  the key columns as sqldb.UUID(b).String(): canonical lowercase text
+ *     written into gen_bytes and interned (as a child row's StartedRunID), so they share
+ *     handles with the same IDs in histories; workflow_id the key column's string.
+ *   10 parent_domain_id, 14 parent_run_id  the same rendering of their 16 bytes; 12
+ *     parent_workflow_id, 16 initiated_id.  All four are read only if field 10 is present
+ *     (:305); else the handles are 0 and initiated_id is EmptyEventID (-23), what every replay
+ *     leaves for a workflow without a parent (the SQL read leaves Go's zero there and the
+ *     Cassandra read -23; nothing reads it, and a loaded state then equals a replayed one).  An
+ *     empty or absent binary is handle 0; a length other than 0 or 16 is CDR_LOAD_E_UUID.
+ *   18 completion_event_batch_id if present, else EmptyEventID (-23) (:270, 320).
+ *   24 task_list, 26 workflow_type, 28 workflow_timeout, 30 decision_timeout_value, 34 state, 36
+ *   close_status, 50 last_first_event_id, 52 last_processed_event, 58 decision_version, 60
+ *   decision_schedule_id, 62 decision_started_id, 64 decision_timeout, 66 decision_attempt, 68
+ *   decision_started_ts, 69 decision_scheduled_ts, 71 decision_original_scheduled_ts, 72
+ *   create_request_id and 74 decision_request_id (plain strings, as the encoder writes them), 84 /
+ *   86 / 88 / 90 initial_interval / maximum_interval / maximum_attempts / expiration_seconds, 92
+ *   backoff_coefficient (the double's bits), 100 cron_schedule.
+ *   next_event_id is the column.  last_event_task_id is 0: the reference's SQL read never
+ *     assigns it (field 48 is written at sqlExecutionManagerUtil.go:1216 and read nowhere), and
+ *     every applyEvents overwrites it.
+ *   82 attempt and 106 signal_count narrowed as Go's int32(): the low 32 bits.
+ *   94 expiration_time: CDR_XI_HAS_EXPIRATION iff the value != CDR_ZERO_TIME_NANOS, and the value
+ *     is kept, else 0 (an absent field is 0: set, time.Unix(0, 0)).
+ *   96 nonretriable: the list's body; an empty list or another element type is handle 0.
+ *   flags: 70 CDR_XI_CANCEL_REQUESTED, 98 CDR_XI_HAS_RETRY (the booleans' values); field 118 /
+ *     120 / 104 present (as a map / map / binary) CDR_XI_HAS_SEARCH_ATTR / _HAS_MEMO /
+ *     _HAS_BRANCH; CDR_XI_HAS_RESET_POINTS iff the ResetPoints struct has its Points field (a
+ *     list of structs); CDR_XI_VH_BRANCH iff the VersionHistory's token is non-empty;
+ *     CDR_XI_STARTED always (an execution row exists only for a started execution).
+ *   120 memo: the handle of the wire body of a Memo struct, 0D 00 0A + the map's body + 00,
+ *     written into gen_bytes (the bytes are not contiguous in the input) and interned from there.
+ *   118 search attributes: cdr_kv rows in wire order; a key that occurs twice keeps the
+ *     position of its first occurrence and the value of its last; n_search_attr (and the
+ *     record's search_attr_len) counts distinct keys, sa_cap is the wire count; every pair's
+ *     strings are interned, a superseded value included.  A map whose key / value types are
+ *     not both string has no rows.
+ *   104 / VersionHistory.BranchToken: the 0x59 preamble (else CDR_LOAD_E_ENCODING, an empty field
+ *     104 included; an empty VersionHistory token is "no token"), then HistoryBranch{10 TreeID ->
+ *     branch_tree_id, 20 BranchID -> branch_id_hi / lo, canonical 36-character text only as the
+ *     request IDs, else CDR_LOAD_E_UUID; 30 Ancestors must be empty}.
+ *   115 / 116 AutoResetPoints and 122 / 124 VersionHistories: the encoding must be "thriftrw" and
+ *     the blob's first byte 0x59, else CDR_LOAD_E_ENCODING; an absent or empty 115 is nil reset
+ *     points (nothing checked).  ResetPointInfo's optional fields 10 .. 60 set the CDR_RP_HAS_*
+ *     bits one for one; reset_points_len = n_reset_points.  The one VersionHistory's items go
+ *     to state.vh in order.  A nested blob is walked level by level: each level's wire errors
+ *     (CDR_DEC_*, bytes after its stop byte ignored) come before any finding inside it.
+ *   builder[w] (a cdr_wf_desc.builder value): CDR_BUILDER_2DC iff field 44 is present (:286) —
+ *     then repl.present = 1, start / current version 38 / 40, last_write_event_id 44,
+ *     last_write_version the column, LastReplicationInfo from field 46 {10 version, 12
+ *     last_event_id} by comparing each key's bytes with the clusters' names (a key that names
+ *     none: CDR_LOAD_E_CLUSTER; a repeated key: the last) — CDR_BUILDER_NDC iff field 122 is
+ *     present, else CDR_BUILDER_LOCAL; state.repl of other builders is zero.
+ *   persist[w] (cdr_exec_persist): 38 start_version, 40 current_version, 54 start_time, 56
+ *     last_updated_time, 108 history_size, 80 sticky_s2s_timeout narrowed through int32 (:263),
+ *     32 execution_context (absent or empty: handle 0), 78 sticky_task_list, 110 / 112 / 114
+ *     client_library_version / client_feature_version / client_impl.
+ *   Parsed over and dropped: 20 / 22 CompletionEvent and its encoding, 76 CancelRequestID, 48.
+ * Statuses of an execution row (exec_status[w]): CDR_DEC_*, CDR_LOAD_E_UUID and the three below,
+ * the first finding in this order: the row's own wire errors; the parent IDs' lengths; fields
+ * 44 and 122 together (SHAPE); an unknown cluster; field 104's token; the reset points'
+ * encoding, preamble, wire errors, count over CDR_LOAD_MAX_RESET_POINTS (SHAPE); search
+ * attributes over CDR_LOAD_MAX_SEARCH_ATTR (SHAPE); the version histories' encoding, preamble,
+ * wire errors, CurrentVersionHistoryIndex != 0 or not exactly one VersionHistory (SHAPE), its
+ * token, field 104 and a non-empty token together (SHAPE), items over CDR_LOAD_MAX_VH_ITEMS
+ * (SHAPE).  The bounds exist for the reason CDR_LOAD_MAX_ENTRY_ROWS does: one lane walks an
+ * entry's items, and search-attribute keys are compared pairwise.
+ * A failing execution row fails its entry exactly as a failing pending row does (CDR_E_LOAD_ROWS,
+ * zero counts, none of the entry's strings interned, other entries unaffected); in the entry's
+ * first-failure order the execution row is table 5, after the pending tables.
+ *
+ * Outputs: everything cdr_rows_out has, with state.exec / repl [n_entries] and state.vh / rp /
+ * sa filled, caps[w].vh_off / rp_off / sa_off and *_cap (the wire counts), result[w].n_vh /
+ * n_reset_points / n_search_attr and totals to match — state, caps and totals are a cdr_carry's
+ * as they are — and persist, builder, exec_status [n_entries].  gen_bytes holds the child rows'
+ * run IDs first (36 * n_rows[2] bytes), then each entry's UUID texts (36 bytes each) and Memo
+ * body (its length + 4, the entry's share rounded up to 4 bytes).  Same lifetime, workspace and
+ * synchronisation as cdr_load_rows, and no host round trip more.  CDR_API_EINVAL also for a
+ * null column of `exec` with n_entries != 0 and n_clusters > CDR_MAX_CLUSTERS. */
+#define CDR_LOAD_E_ENCODING 19 /* a nested blob's encoding is not thriftrw / its 0x59 preamble is missing */
+#define CDR_LOAD_E_SHAPE 20    /* a valid row the records cannot hold */
+#define CDR_LOAD_E_CLUSTER 21  /* a LastReplicationInfo key names none of the clusters */
+#define CDR_LOAD_MAX_VH_ITEMS 16384u
+#define CDR_LOAD_MAX_RESET_POINTS 1024u
+#define CDR_LOAD_MAX_SEARCH_ATTR 256u
+typedef struct cdr_exec_rows_in { /* device pointers */
+  const uint64_t* blob_off;        /* [n_entries + 1] into rows->bytes */
+  const uint8_t* domain_id;        /* [16 * n_entries] */
+  const uint8_t* run_id;           /* [16 * n_entries] */
+  const uint64_t* workflow_id_off; /* [n_entries + 1] into rows->bytes */
+  const int64_t* next_event_id;    /* [n_entries] */
+  const int64_t* last_write_version; /* [n_entries] */
+  uint32_t cluster_seed[CDR_MAX_CLUSTERS];
+  uint32_t n_clusters, _pad;
+} cdr_exec_rows_in;
+typedef struct cdr_state_out { /* device buffers owned by the context */
+  cdr_rows_out rows;
+  cdr_exec_persist* persist; /* [n_entries] */
+  uint32_t* builder;         /* [n_entries] */
+  int32_t* exec_status;      /* [n_entries] */
+} cdr_state_out;
+int cdr_load_state(cdr_ctx* ctx, const cdr_rows_in* rows, const cdr_exec_rows_in* exec, cdr_state_out* out,
+                   void* stream);
+
+/* Device milliseconds of the last cdr_load_rows / cdr_load_state on the context, between HIP events on its
  * stream: ms[0] the count pass (with the row -> entry map), ms[1] the intern pass and the
  * string ranking (with the two host round trips that size the table and the sort), ms[2] the
  * row ranking, ms[3] the fill pass and the entry epilogue.  The call is synchronous and holds

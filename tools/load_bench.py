@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Throughput of the persisted-row loader (cdr_load_rows) beside the history ingest
+"""Throughput of the persisted-row loader (cdr_load_rows) and the whole-state loader
+(cdr_load_state: the same rows plus every workflow's execution row) beside the history ingest
 (cdr_ingest_decode), the comparable lane-per-blob thrift walk, on the same populations.
 
 States: the final states of a config-3 and a config-5 replay.  --base workflows are
@@ -10,6 +11,10 @@ strings: the loader interns base-many distinct strings however many rows name th
 store full of shared task lists and types would, but the per-workflow IDs of a real store
 would add distinct strings the tiles do not have: a second run appends the entry number to
 every timer ID, which makes the timer table's key strings distinct per workflow.  Seeds: "" alone, so every string is new.
+Each population is loaded again with its execution rows (cdr_load_state, "load_state" in the
+record); in the distinct run every workflow also has a run ID of its own, one more distinct
+string per workflow.  "added" is the execution rows' cost: the whole-state call's wall time
+less cdr_load_rows' on the same pending rows, and the execution rows' bytes over it.
 
 Each call is timed wall-clock (it is synchronous) on a warm context over --reps repeats;
 the passes inside it by the HIP events cdr_load_pass_ms reads.  The ingest decodes the same
@@ -80,13 +85,35 @@ def distinct_timer_ids(R: rows.Rows) -> rows.Rows:
                      R.n_entries)
 
 
+def with_exec_rows(R: rows.Rows, X: rows.Rows, tile: int, distinct: bool) -> rows.Rows:
+    """R (tiled) with the execution rows of X (one population, untiled) `tile` times over behind
+    its bytes: workflow IDs, then the blobs.  distinct: every entry's run ID is its own."""
+    x = X.exec
+    pos = len(R.bytes)
+    wid = tile_offsets(x.workflow_id_off, tile, pos, np.uint64)
+    wseg = np.tile(X.bytes[int(x.workflow_id_off[0]):int(x.workflow_id_off[-1])], tile)
+    off = tile_offsets(x.blob_off, tile, pos + len(wseg), np.uint64)
+    bseg = np.tile(X.bytes[int(x.blob_off[0]):int(x.blob_off[-1])], tile)
+    run = np.tile(x.run_id, tile)
+    if distinct:
+        run = run.reshape(-1, 16).copy()
+        run[:, :4] = np.arange(len(run), dtype=">u4").view(np.uint8).reshape(-1, 4)
+        run = run.reshape(-1)
+    xr = rows.ExecRows(off, np.tile(x.domain_id, tile), run, wid, np.tile(x.next_event_id, tile),
+                       np.tile(x.last_write_version, tile), x.cluster_seed)
+    return rows.Rows(np.concatenate([R.bytes, wseg, bseg]), R.blob_off, R.entry_row0, R.key, R.timer_id_off,
+                     R.act_heartbeat, R.n_entries, exec=xr)
+
+
 def time_load(eng, R: rows.Rows, reps: int) -> dict:
-    """cdr_load_rows over R (seeds: "" alone), wall clock and passes."""
+    """cdr_load_rows over R — cdr_load_state where R has execution rows — (seeds: "" alone),
+    wall clock and passes."""
     L = abi.lib()
     n_rows, n_bytes = R.n_rows, int(len(R.bytes))
     dev = rows.DeviceBuffers()
     try:
-        sb, so = ingest.string_table([b""])
+        seeds = [b""] + (list(R.exec.cluster_seed) if R.exec is not None else [])  # (held as names here)
+        sb, so = ingest.string_table(seeds)
         inp = abi.CdrRowsIn()
         inp.bytes, inp.n_bytes = dev.up(R.bytes), n_bytes
         for t in range(5):
@@ -95,13 +122,26 @@ def time_load(eng, R: rows.Rows, reps: int) -> dict:
             inp.n_rows[t] = n_rows[t]
         inp.timer_id_off, inp.act_heartbeat = dev.up(R.timer_id_off), dev.up(R.act_heartbeat)
         inp.seed_bytes, inp.seed_off = dev.up(sb), dev.up(so)
-        inp.n_entries, inp.n_seeds = R.n_entries, 1
+        inp.n_entries, inp.n_seeds = R.n_entries, len(seeds)
         wall, passes = [], [[] for _ in PASSES]
         res = abi.CdrRowsOut()
+        X = R.exec
+        if X is not None:
+            sout, xin = abi.CdrStateOut(), abi.CdrExecRowsIn()
+            xin.blob_off, xin.workflow_id_off = dev.up(X.blob_off), dev.up(X.workflow_id_off)
+            xin.domain_id, xin.run_id = dev.up(X.domain_id), dev.up(X.run_id)
+            xin.next_event_id, xin.last_write_version = dev.up(X.next_event_id), dev.up(X.last_write_version)
+            xin.n_clusters = len(seeds) - 1
+            for i in range(xin.n_clusters):
+                xin.cluster_seed[i] = 1 + i
         for rep in range(reps + 1):
             assert dev.hip.hipDeviceSynchronize() == 0
             t0 = time.perf_counter()
-            rc = L.cdr_load_rows(eng.ctx, C.byref(inp), C.byref(res), None)
+            if X is not None:
+                rc = L.cdr_load_state(eng.ctx, C.byref(inp), C.byref(xin), C.byref(sout), None)
+                res = sout.rows
+            else:
+                rc = L.cdr_load_rows(eng.ctx, C.byref(inp), C.byref(res), None)
             t1 = time.perf_counter()
             assert rc == 0 and res.n_bad_entries == 0, (rc, res.n_bad_entries)
             ms = (C.c_float * 4)()
@@ -113,7 +153,7 @@ def time_load(eng, R: rows.Rows, reps: int) -> dict:
         n_strings = int(res.n_strings)
     finally:
         dev.free()
-    total_rows = sum(n_rows)
+    total_rows = sum(n_rows) + (R.n_entries if X is not None else 0)
     w = stats(wall)
     rec = {"bytes": n_bytes, "strings": n_strings, "load_wall_s": w, "load_gbs": n_bytes / w["median"] / 1e9,
            "load_rows_per_s": total_rows / w["median"], "passes": {}}
@@ -122,7 +162,17 @@ def time_load(eng, R: rows.Rows, reps: int) -> dict:
         rec["passes"][name] = {"s": s, "rows_per_s": total_rows / s["median"]}
         if name != "rank_rows":  # (it reads keys, not blob bytes)
             rec["passes"][name]["gbs"] = n_bytes / s["median"] / 1e9
+    if X is not None:
+        rec["exec_rows"] = R.n_entries
+        rec["exec_bytes"] = int(X.blob_off[-1] - X.workflow_id_off[0])
     return rec
+
+
+def added(state: dict, plain: dict) -> dict:
+    """What the execution rows add to the call."""
+    s = state["load_wall_s"]["median"] - plain["load_wall_s"]["median"]
+    return {"ms": s * 1e3, "gbs": state["exec_bytes"] / s / 1e9 if s > 0 else None,
+            "passes_ms": {p: (state["passes"][p]["s"]["median"] - plain["passes"][p]["s"]["median"]) * 1e3 for p in PASSES}}
 
 
 def bench_config(eng, cfg: int, base: int, tile: int, reps: int, ingest_bytes: int) -> dict:
@@ -136,7 +186,19 @@ def bench_config(eng, cfg: int, base: int, tile: int, reps: int, ingest_bytes: i
     rec.update(time_load(eng, R, reps))
     # the same rows with the timer IDs distinct per workflow: the intern pass inserts and the
     # ranking sorts millions of strings instead of finding a few thousand again and again
-    rec["distinct_timer_ids"] = time_load(eng, distinct_timer_ids(R), reps)
+    D = distinct_timer_ids(R)
+    rec["distinct_timer_ids"] = time_load(eng, D, reps)
+    # ---- the same two populations with their execution rows (cdr_load_state); the cluster
+    # names are the only seeds beside ""
+    n_cl = b.cluster.n_clusters
+    xs = rows.whole_state_strings(b, out, extra=n_cl)
+    X = rows.encode_state(eng, b, out, xs, exec_rows=True, cluster_names=list(range(len(xs) - n_cl, len(xs))))
+    X.exec.cluster_seed = xs[len(xs) - n_cl:]
+    rec["load_state"] = time_load(eng, with_exec_rows(R, X, tile, False), reps)
+    rec["load_state"]["added"] = added(rec["load_state"], rec)
+    rec["distinct_timer_ids"]["load_state"] = time_load(eng, with_exec_rows(D, X, tile, True), reps)
+    rec["distinct_timer_ids"]["load_state"]["added"] = added(rec["distinct_timer_ids"]["load_state"],
+                                                             rec["distinct_timer_ids"])
     # ---- the history ingest of the same population
     enc = ingest.encode_batch(b, threads=16)
     raw = enc.blob_bytes[:int(enc.blob_off[-1])]
@@ -189,7 +251,7 @@ def main():
     rec = {"tool": "tools/load_bench.py", "device": box, "libcdr": abi.lib().cdr_version().decode(),
            "build_flags": int(abi.lib().cdr_build_flags()), "reps": args.reps,
            "timing": "wall clock around the synchronous calls on a warm context (first call dropped); passes: HIP "
-                     "events inside cdr_load_rows (the intern interval holds its two host round trips)",
+                     "events inside cdr_load_rows / cdr_load_state (the intern interval holds its two host round trips)",
            "seeds": 1, "configs": []}
     for cfg in (int(c) for c in args.configs.split(",")):
         r = bench_config(eng, cfg, args.base, args.tile, args.reps, args.ingest_bytes)
