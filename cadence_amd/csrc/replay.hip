@@ -2001,6 +2001,7 @@ __global__ void k_finalize(cdr_dev_batch B, cdr_out O) {
       P.fail_index = C.fail_index;
       P.n_activity = P.n_timer = P.n_child = P.n_cancel = P.n_signal = 0;
       P.n_vh = P.n_reset_points = P.n_search_attr = 0;
+      if (O.n_tasks) O.n_tasks[2ull * w] = O.n_tasks[2ull * w + 1] = 0;  // a failed entry reports no tasks
     }
   } else {
     C.code = CDR_NOT_APPLIED;
@@ -2008,6 +2009,7 @@ __global__ void k_finalize(cdr_dev_batch B, cdr_out O) {
     C.fail_index = 0;
     C.n_activity = C.n_timer = C.n_child = C.n_cancel = C.n_signal = 0;
     C.n_vh = C.n_reset_points = C.n_search_attr = 0;
+    if (O.n_tasks) O.n_tasks[2ull * (uint32_t)c] = O.n_tasks[2ull * (uint32_t)c + 1] = 0;
   }
   C.flags = CDR_RF_IS_NEWRUN;
 }

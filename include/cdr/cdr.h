@@ -219,7 +219,10 @@ typedef struct cdr_slices {
   (CDR_TB(CDR_EV_DT_SCHEDULED) | CDR_TB(CDR_EV_DT_TIMED_OUT) | CDR_TB(CDR_EV_AT_SCHEDULED) | CDR_TB(CDR_EV_CHILD_INITIATED))
 /* type_flags word of an event: type, flags and its column-need bits */
 CDR_HD uint32_t cdr_type_flags(uint32_t type, uint32_t flags) {
-  uint32_t tf = (type & 0xFFu) | flags;
+  /* the type byte: a caller's type of 255 (the padding value) or past the byte (256 would alias
+   * WorkflowExecutionStarted) is as unknown as any (stateBuilder.go:597-599) and travels as 254,
+   * which no kernel knows and none takes for padding */
+  uint32_t tf = (type >= (uint32_t)CDR_EV_PAD ? 0xFEu : type) | flags;
   if (type < 64) {
     const uint64_t b = 1ull << type;
     tf |= ((CDR_NEED_TS & b) ? CDR_SEF_NEED_TS : 0u) | ((CDR_NEED_KEY & b) ? CDR_SEF_NEED_KEY : 0u) |

@@ -1,9 +1,13 @@
 """GPU parity: the HIP replay engine vs the CPU restatement (oracle/), field by field.
 
 Inputs are the deterministic synthetic configs of SURVEY §8(d) (small sizes the
-oracle finishes in seconds), with and without injected faults so that every error
-and panic site is exercised.  Bar: bit-exact (integer/handle state; the only float,
-BackoffCoefficient, is a verbatim copy).
+oracle finishes in seconds), with and without injected faults.  The injected faults
+(synth.cpp inject_fault: eight mutations of the parent history at a random index >= 2)
+reach only some of the error and panic sites — no missing domain, no duplicate
+activityId, no version-history event-id or item error, one of the state-transition
+sites, nothing inside a new run or at index 0 or 1; tests/test_fault_sites.py pins every
+site with hand-built histories on every kernel route.  Bar: bit-exact (integer/handle
+state; the only float, BackoffCoefficient, is a verbatim copy).
 """
 import pytest
 
