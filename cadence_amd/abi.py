@@ -230,6 +230,14 @@ CdrExecRowsIn = _S("cdr_exec_rows_in", [
     ("n_clusters", u32), ("_pad", u32)])
 CdrStateOut = _S("cdr_state_out", [
     ("rows", CdrRowsOut), ("persist", C.c_void_p), ("builder", C.c_void_p), ("exec_status", C.c_void_p)])
+# the Cassandra form of the pending tables (cdr.h cdr_load_cql_rows)
+LOAD_E_CQL_SIZE = 22
+LOAD_STATUS[22] = "E_CQL_SIZE"
+CdrCqlRowsIn = _S("cdr_cql_rows_in", [
+    ("bytes", C.c_void_p), ("n_bytes", u64), ("col_off", C.c_void_p * LOAD_TABLES), ("seed_bytes", C.c_void_p),
+    ("seed_off", C.c_void_p), ("n_entries", u32), ("n_seeds", u32)])
+CdrCqlRowsOut = _S("cdr_cql_rows_out", [
+    ("rows", CdrRowsOut), ("entry_row0", C.c_void_p * LOAD_TABLES), ("n_rows", u32 * LOAD_TABLES), ("_pad", u32)])
 CdrOpts = _S("cdr_opts", [("plan_mode", u32), ("fast_path", i32), ("reg_path", i32), ("concurrent", i32),
                           ("workspace_bytes", u64)])
 CdrVHToken = _S("cdr_vh_token", [("tree", u32), ("_pad", u32), ("branch_lo", u64), ("branch_hi", u64)])
@@ -388,6 +396,7 @@ MIRRORS = {
     "cdr_sync_activity": CdrSyncActivity, "cdr_sync_result": CdrSyncResult,
     "cdr_rows_in": CdrRowsIn, "cdr_rows_out": CdrRowsOut,
     "cdr_exec_rows_in": CdrExecRowsIn, "cdr_state_out": CdrStateOut,
+    "cdr_cql_rows_in": CdrCqlRowsIn, "cdr_cql_rows_out": CdrCqlRowsOut,
 }
 
 # C ABI entry points declared in include/cdr/cdr.h and include/cdr/synth.h
@@ -473,6 +482,7 @@ EXPORTS = {
     "cdr_load_rows": (i32, [C.c_void_p, C.POINTER(CdrRowsIn), C.POINTER(CdrRowsOut), C.c_void_p]),
     "cdr_load_state": (i32, [C.c_void_p, C.POINTER(CdrRowsIn), C.POINTER(CdrExecRowsIn), C.POINTER(CdrStateOut),
                              C.c_void_p]),
+    "cdr_load_cql_rows": (i32, [C.c_void_p, C.POINTER(CdrCqlRowsIn), C.POINTER(CdrCqlRowsOut), C.c_void_p]),
     "cdr_load_pass_ms": (i32, [C.c_void_p, C.POINTER(C.c_float)]),
     "cdr_strtab_gather_async": (i32, [C.c_void_p, C.c_void_p, C.c_void_p, u32, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -61,6 +61,9 @@ enum cdr_ws_slot {
   // cdr_load_state: the execution rows' records, item tables, per-entry counts and their scan
   WS_LD_EXEC, WS_LD_REPL, WS_LD_PERSIST, WS_LD_BUILDER, WS_LD_XSTATUS, WS_LD_VH, WS_LD_RP, WS_LD_SA, WS_LD_NSA,
   WS_LD_XCNT, WS_LD_XOFF, WS_LD_XTMP,
+  // cdr_load_cql_rows: the map split's pair counts, their scans (entry_row0), its failure words,
+  // the generated row offsets and keys, and the activity rows' list-body sizes and offsets
+  WS_LD_CQ_CNT, WS_LD_CQ_ROW0, WS_LD_CQ_FAIL, WS_LD_CQ_OFF, WS_LD_CQ_KEY, WS_LD_CQ_GNEED, WS_LD_CQ_GOFF,
   WS_GATHER_TMP,  // cdr_strtab_gather_async: the offset scan's temporary storage
   WS_NUM
 };

@@ -1227,6 +1227,8 @@ uint64_t cdr_struct_size(const char* name) {
       {"cdr_rows_out", sizeof(cdr_rows_out)},
       {"cdr_exec_rows_in", sizeof(cdr_exec_rows_in)},
       {"cdr_state_out", sizeof(cdr_state_out)},
+      {"cdr_cql_rows_in", sizeof(cdr_cql_rows_in)},
+      {"cdr_cql_rows_out", sizeof(cdr_cql_rows_out)},
   };
   for (const E& e : table)
     if (std::strcmp(e.n, name) == 0) return e.s;

@@ -18,6 +18,13 @@
 //   4. FILL    each record built in registers and stored whole at its ranked slot.
 // An epilogue, one lane per entry, writes result / caps / entry_status from the failure words
 // and the row ranges alone: it walks no rows.
+//
+// The Cassandra form of the pending tables (cdr_load_cql_rows) is a second front end of the
+// same passes: a pre-pass, one lane per (entry, table), splits each map column into its pairs
+// (k_cql_split: count, one scan per table, then the row offsets), and Row<TBL>::parse_cql walks
+// a pair's UDT — a fixed sequence of length-prefixed values, straight-line code — into the same
+// record and Spans.  Keys come from the UDT (the count pass writes them out for the ranking),
+// and an activity's error list, whose bytes lack the thrift type byte, goes through gen_bytes.
 #include <hip/hip_runtime.h>
 
 #include <hipcub/hipcub.hpp>
@@ -76,6 +83,11 @@ struct LCtx {  // per launch (one table)
   void* recs;                  // FILL: the table
   int64_t* tkey;               // table 1: INTERN writes the ID's hash, FILL reads its handle
   uint32_t n_rows, n_entries;
+  // the Cassandra form only
+  int64_t* key_out;            // tables 0, 2-4: COUNT writes the UDT's key field ([n_rows]; = key)
+  uint64_t* gneed;             // table 0: COUNT writes the row's list-body bytes in gen_bytes
+  const uint64_t* goff;        // its exclusive scan, [n_rows + 1]
+  uint64_t gen_base;           // where the list bodies start in gen_bytes
 };
 
 __device__ __forceinline__ unsigned long long fail_word(uint32_t table, uint32_t row_in_entry, int32_t status) {
@@ -161,6 +173,129 @@ __device__ __forceinline__ uint64_t uuid_text_hash(Rd& r, uint64_t at) {  // cdr
   return h ? h : 1u;
 }
 
+// ---------------------------------------------------------------- CQL values
+// (cdr.h cdr_load_cql_rows) the reader stands inside a UDT value: [pos, end) are its fields
+// the next field's [bytes]: false = null, absent (the UDT ended: fewer fields) or an error
+__device__ __forceinline__ bool cq_val(Rd& r, Span* v) {
+  *v = Span{0, 0};
+  if (!r.ok() || r.pos == r.end) return false;
+  const int32_t len = (int32_t)r.be32();
+  if (!r.ok()) return false;
+  if (len < 0) {
+    if (len != -1) r.err = CDR_DEC_BAD_SIZE;
+    return false;
+  }
+  if (!r.need((uint32_t)len)) return false;
+  *v = Span{r.pos, (uint32_t)len};
+  r.pos += (uint32_t)len;
+  return true;
+}
+// a fixed-size value: false = the type's zero (null, empty, or an error)
+__device__ __forceinline__ bool cq_fixed(Rd& r, uint32_t size, Span* v) {
+  if (!cq_val(r, v) || v->n == 0) return false;
+  if (v->n != size) {
+    r.err = CDR_LOAD_E_CQL_SIZE;
+    return false;
+  }
+  return true;
+}
+__device__ __forceinline__ uint64_t be64_at(Rd& r, uint64_t at) {
+  uint64_t v = 0;
+  for (uint32_t i = 0; i < 8; i++) v = (v << 8) | r.at(at + i);
+  return v;
+}
+__device__ __forceinline__ uint32_t be32_at(Rd& r, uint64_t at) {
+  return (r.at(at) << 24) | (r.at(at + 1) << 16) | (r.at(at + 2) << 8) | r.at(at + 3);
+}
+__device__ __forceinline__ int64_t cq_i64(Rd& r) {
+  Span v;
+  return cq_fixed(r, 8, &v) ? (int64_t)be64_at(r, v.at) : 0;
+}
+__device__ __forceinline__ int32_t cq_i32(Rd& r) {
+  Span v;
+  return cq_fixed(r, 4, &v) ? (int32_t)be32_at(r, v.at) : 0;
+}
+__device__ __forceinline__ uint32_t cq_bool(Rd& r, uint32_t bit) {
+  Span v;
+  return cq_fixed(r, 1, &v) && r.at(v.at) ? bit : 0u;
+}
+// a timestamp, milliseconds -> UnixNano; null or empty: Go's zero time
+__device__ __forceinline__ int64_t cq_time(Rd& r) {
+  Span v;
+  if (!cq_fixed(r, 8, &v)) return CDR_ZERO_TIME_NANOS;
+  const int64_t ms = (int64_t)be64_at(r, v.at);
+  if (ms > 9223372036854ll || ms < -9223372036854ll) {  // ms * 1e6 leaves int64
+    r.err = CDR_LOAD_E_SHAPE;
+    return 0;
+  }
+  return ms * 1000000ll;
+}
+__device__ __forceinline__ Span cq_text(Rd& r) {  // text / blob: null is ""
+  Span v;
+  cq_val(r, &v);
+  return v.n ? v : Span{0, 0};
+}
+// list<text>: the value's bytes from its count to the end of its last element (the thrift
+// list<string> body without its type byte); null, empty or count 0: none
+__device__ __forceinline__ Span cq_list_text(Rd& r) {
+  Span v;
+  if (!cq_val(r, &v) || v.n == 0) return Span{0, 0};
+  uint64_t p = v.at;
+  const uint64_t e = v.at + v.n;
+  if (e - p < 4) {
+    r.err = CDR_DEC_TRUNCATED;
+    return Span{0, 0};
+  }
+  const int32_t cnt = (int32_t)be32_at(r, p);
+  p += 4;
+  if (cnt < 0) {
+    r.err = CDR_DEC_BAD_SIZE;
+    return Span{0, 0};
+  }
+  for (int32_t k = 0; k < cnt; k++) {
+    if (e - p < 4) {
+      r.err = CDR_DEC_TRUNCATED;
+      return Span{0, 0};
+    }
+    const int32_t len = (int32_t)be32_at(r, p);
+    p += 4;
+    if (len < 0) {  // a null element included
+      r.err = CDR_DEC_BAD_SIZE;
+      return Span{0, 0};
+    }
+    if (e - p < (uint64_t)len) {
+      r.err = CDR_DEC_TRUNCATED;
+      return Span{0, 0};
+    }
+    p += (uint64_t)len;
+  }
+  return cnt ? Span{v.at, (uint32_t)(p - v.at)} : Span{0, 0};
+}
+// cdr_str_hash of 0B + the list body b; the bytes go to `out` as well when it is not null
+// (inline: a call would take the reader by address and so move it to scratch for the whole row)
+__device__ __forceinline__ uint64_t list_hash(Rd& r, Span b, uint8_t* out) {
+  uint64_t h = 0xCBF29CE484222325ull;
+  const uint64_t n = (uint64_t)b.n + 1;
+  for (uint64_t i = 0; i < n; i++) {
+    const uint32_t c = i == 0 ? (uint32_t)T_STRING : r.at(b.at + (i - 1));
+    h = (h ^ c) * 0x100000001B3ull;
+    if (out) out[i] = (uint8_t)c;
+  }
+  h = cdr_mix64(h ^ (n * 0x9E3779B97F4A7C15ull));
+  return h ? h : 1u;
+}
+// one [bytes] of a map's pair delimited (the key, then the UDT): its length, -1 = null
+__device__ __forceinline__ int32_t cq_delimit(Rd& r) {
+  const int32_t len = (int32_t)r.be32();
+  if (!r.ok()) return -1;
+  if (len < -1) {
+    r.err = CDR_DEC_BAD_SIZE;
+    return -1;
+  }
+  if (len > 0 && r.need((uint32_t)len)) r.pos += (uint32_t)len;
+  return len;
+}
+
 // ---------------------------------------------------------------- the rows
 template <int TBL> struct RecOf;
 template <> struct RecOf<0> { typedef cdr_activity_info type; };
@@ -177,6 +312,119 @@ struct Row {
   Span uu;            // the request-ID text (tables 2-4)
   Span run;           // table 2: StartedRunID
   int64_t started26;  // table 0: StartedTimeNanos (absent: 0)
+  int64_t hb_ns;      // table 0, Cassandra form: last_hb_updated_time as UnixNano
+  Span tid;           // table 1, Cassandra form: timer_id
+
+  __device__ __forceinline__ void clear() {
+    uint64_t* z = reinterpret_cast<uint64_t*>(&rec);
+#pragma unroll
+    for (uint32_t i = 0; i < sizeof(rec) / 8; i++) z[i] = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) sp[i] = Span{0, 0};
+    uu = run = tid = Span{0, 0};
+    started26 = 0;
+    hb_ns = CDR_ZERO_TIME_NANOS;
+  }
+
+  // The Cassandra form: r stands at a map pair (the key's length word).  The key is stepped
+  // over, the UDT's length bounds the walk, and the fields come in declaration order
+  // (schema.cql:149-228), each one bounded [bytes] read; the first finding stops the walk.
+  __device__ __forceinline__ void parse_cql(Rd& r) {
+    clear();
+    cq_delimit(r);
+    {
+      const int32_t len = (int32_t)r.be32();
+      if (r.ok() && len < -1) r.err = CDR_DEC_BAD_SIZE;
+      if (!r.ok()) return;
+      if (len > 0 && !r.need((uint32_t)len)) return;
+      r.end = r.pos + (len > 0 ? (uint32_t)len : 0u);
+    }
+    if constexpr (TBL == 0) {  // activity_info
+      cdr_activity_info& a = rec;
+      a.version = cq_i64(r);
+      a.schedule_id = cq_i64(r);
+      a.scheduled_event_batch_id = cq_i64(r);
+      cq_text(r);  // scheduled_event
+      a.scheduled_time = cq_time(r);
+      a.started_id = cq_i64(r);
+      cq_text(r);  // started_event
+      started26 = cq_time(r);
+      sp[0] = cq_text(r);
+      sp[1] = cq_text(r);
+      cq_text(r);  // details
+      a.s2s = cq_i32(r);
+      a.s2c = cq_i32(r);
+      a.stc = cq_i32(r);
+      a.hb = cq_i32(r);
+      a.flags |= cq_bool(r, CDR_AI_CANCEL_REQUESTED);
+      a.cancel_request_id = cq_i64(r);
+      hb_ns = cq_time(r);
+      a.timer_task_status = cq_i32(r);
+      a.attempt = cq_i32(r);
+      sp[2] = cq_text(r);
+      cq_text(r);  // started_identity
+      a.flags |= cq_bool(r, CDR_AI_HAS_RETRY);
+      a.initial_interval = cq_i32(r);
+      a.backoff_coefficient = __longlong_as_double((long long)cq_i64(r));
+      a.maximum_interval = cq_i32(r);
+      a.expiration_time = cq_time(r);
+      a.maximum_attempts = cq_i32(r);
+      sp[3] = cq_list_text(r);
+      cq_text(r);  // last_failure_reason
+      cq_text(r);  // last_worker_identity
+      cq_text(r);  // last_failure_details
+      cq_text(r);  // event_data_encoding
+    } else if constexpr (TBL == 1) {  // timer_info
+      cdr_timer_info& x = rec;
+      x.version = cq_i64(r);
+      tid = cq_text(r);
+      x.started_id = cq_i64(r);
+      x.expiry_time = cq_time(r);
+      x.task_id = cq_i64(r);
+    } else if constexpr (TBL == 2) {  // child_execution_info
+      cdr_child_info& c = rec;
+      c.version = cq_i64(r);
+      c.initiated_id = cq_i64(r);
+      c.initiated_event_batch_id = cq_i64(r);
+      cq_text(r);  // initiated_event
+      c.started_id = cq_i64(r);
+      sp[0] = cq_text(r);
+      Span u;
+      if (cq_fixed(r, 16, &u)) {  // started_run_id: zero and the writer's emptyRunID are none
+        const uint64_t hi = be64_at(r, u.at), lo = be64_at(r, u.at + 8);
+        const bool none = (hi == 0 && lo == 0) || (hi == 0x30000000'0000'f000ull && lo == 0xf000'000000000000ull);
+        run = none ? Span{0, 0} : u;
+      }
+      cq_text(r);  // started_event
+      if (cq_fixed(r, 16, &u)) {
+        c.create_request_hi = be64_at(r, u.at);
+        c.create_request_lo = be64_at(r, u.at + 8);
+      }
+      cq_text(r);  // event_data_encoding
+      sp[1] = cq_text(r);
+      sp[2] = cq_text(r);
+      c.parent_close_policy = cq_i32(r);
+    } else if constexpr (TBL == 3) {  // request_cancel_info
+      cdr_cancel_info& c = rec;
+      c.version = cq_i64(r);
+      c.initiated_event_batch_id = cq_i64(r);
+      c.initiated_id = cq_i64(r);
+      uu = cq_text(r);
+    } else {  // signal_info
+      cdr_signal_info& g = rec;
+      g.version = cq_i64(r);
+      g.initiated_event_batch_id = cq_i64(r);
+      g.initiated_id = cq_i64(r);
+      Span u;
+      if (cq_fixed(r, 16, &u)) {
+        g.signal_request_hi = be64_at(r, u.at);
+        g.signal_request_lo = be64_at(r, u.at + 8);
+      }
+      sp[0] = cq_text(r);
+      sp[1] = cq_text(r);
+      sp[2] = cq_text(r);
+    }
+  }
 
   __device__ __forceinline__ void parse(Rd& r) {
     uint64_t* z = reinterpret_cast<uint64_t*>(&rec);
@@ -282,7 +530,7 @@ struct Row {
   }
 };
 
-template <int TBL, int P>
+template <int TBL, int P, bool CQL>
 __global__ __launch_bounds__(CDR_LOAD_BLOCK) void k_rows(LCtx C) {
   const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
@@ -300,14 +548,23 @@ __global__ __launch_bounds__(CDR_LOAD_BLOCK) void k_rows(LCtx C) {
     const bool live = P == COUNT || (C.fail[w] == NO_FAIL && (P == INTERN || C.fail[C.n_entries + w] == NO_FAIL));
     if (live) {
       Rd rd;
-      const uint64_t e = umin64(C.blob_off[r + 1], C.total), p = umin64(C.blob_off[r], e);
+      // (the Cassandra form: the pair's own lengths, checked by the split, bound the walk)
+      const uint64_t e = CQL ? C.total : umin64(C.blob_off[r + 1], C.total), p = umin64(C.blob_off[r], e);
       rd.init(C.bytes, p, e, C.total);
       rd.sb = (const LDS3 uint8_t*)stage;
       rd.s_lo = s_lo;
       rd.s_n = s_n;
       Row<TBL> x;
-      x.parse(rd);
+      if constexpr (CQL) x.parse_cql(rd);
+      else x.parse(rd);
       int32_t err = rd.err;
+      if constexpr (CQL && TBL != 1) {  // the key is the UDT's own field
+        if constexpr (TBL == 0) {
+          if (P == COUNT) C.key_out[r] = x.rec.schedule_id;
+        } else {
+          if (P == COUNT) C.key_out[r] = x.rec.initiated_id;
+        }
+      }
       // a handle field by pass: counted, interned, or looked up
       auto H = [&](Span s) -> uint32_t {
         if (s.n == 0) return 0u;
@@ -325,21 +582,42 @@ __global__ __launch_bounds__(CDR_LOAD_BLOCK) void k_rows(LCtx C) {
       if (err == CDR_DEC_OK) {
         if constexpr (TBL == 0) {
           cdr_activity_info& a = x.rec;
-          a.schedule_id = C.key[r];
+          if constexpr (!CQL) a.schedule_id = C.key[r];
           if (x.started26 != CDR_ZERO_TIME_NANOS) {
             a.flags |= CDR_AI_STARTED_TIME_SET;
             a.started_time = x.started26;
           }
-          const int64_t hb = C.hb[r];
+          const int64_t hb = CQL ? x.hb_ns : C.hb[r];
           a.last_heartbeat_time = hb != CDR_ZERO_TIME_NANOS ? hb : 0;
           if (a.last_heartbeat_time != 0 && !(a.flags & CDR_AI_STARTED_TIME_SET)) a.flags |= CDR_AI_HEARTBEAT_TIME_SET;
           a.activity_id = H(x.sp[0]);
           a.request_id = H(x.sp[1]);
           a.task_list = H(x.sp[2]);
-          a.nonretriable = H(x.sp[3]);
+          if constexpr (CQL) {  // the list body gets its type byte in the row's share of gen_bytes
+            const Span b = x.sp[3];
+            if (P == COUNT) {
+              n_str += b.n ? 1u : 0u;
+              C.gneed[r] = b.n ? (uint64_t)b.n + 1 : 0u;
+            } else if (b.n) {
+              if (P == INTERN) {
+                const uint64_t g = C.goff[r];
+                if (g + b.n + 1 <= C.goff[r + 1]) {
+                  const uint64_t h = list_hash(rd, b, C.gen + C.gen_base + g);
+                  tab_insert(C.T, h, (C.gen_base + g) | GEN_REF, b.n + 1, UNASSIGNED);
+                }
+              } else {
+                a.nonretriable = tab_lookup(C.T, list_hash(rd, b, nullptr));
+              }
+            }
+          } else {
+            a.nonretriable = H(x.sp[3]);
+          }
         } else if constexpr (TBL == 1) {
-          const uint64_t e2 = umin64(C.tid_off[r + 1], C.total), p2 = umin64(C.tid_off[r], e2);
-          const Span id{p2, (uint32_t)(e2 - p2)};
+          Span id = x.tid;
+          if constexpr (!CQL) {
+            const uint64_t e2 = umin64(C.tid_off[r + 1], C.total), p2 = umin64(C.tid_off[r], e2);
+            id = Span{p2, (uint32_t)(e2 - p2)};
+          }
           if (P == COUNT) n_str += id.n ? 1u : 0u;
           if (P == INTERN) {
             const uint64_t h = id.n ? rd.hash(id.at, id.n) : 0ull;
@@ -349,9 +627,11 @@ __global__ __launch_bounds__(CDR_LOAD_BLOCK) void k_rows(LCtx C) {
           if (P == FILL) x.rec.timer_id = (uint32_t)C.tkey[r];
         } else if constexpr (TBL == 2) {
           cdr_child_info& c = x.rec;
-          c.initiated_id = C.key[r];
-          if (!parse_uuid(rd, x.uu, &c.create_request_lo, &c.create_request_hi)) err = CDR_LOAD_E_UUID;
-          if (x.run.n != 0 && x.run.n != 16) err = CDR_LOAD_E_UUID;
+          if constexpr (!CQL) {
+            c.initiated_id = C.key[r];
+            if (!parse_uuid(rd, x.uu, &c.create_request_lo, &c.create_request_hi)) err = CDR_LOAD_E_UUID;
+            if (x.run.n != 0 && x.run.n != 16) err = CDR_LOAD_E_UUID;
+          }
           if (err == CDR_DEC_OK) {
             c.started_workflow_id = H(x.sp[0]);
             c.domain_name = H(x.sp[1]);
@@ -371,12 +651,14 @@ __global__ __launch_bounds__(CDR_LOAD_BLOCK) void k_rows(LCtx C) {
           }
         } else if constexpr (TBL == 3) {
           cdr_cancel_info& c = x.rec;
-          c.initiated_id = C.key[r];
+          if constexpr (!CQL) c.initiated_id = C.key[r];
           if (!parse_uuid(rd, x.uu, &c.cancel_request_lo, &c.cancel_request_hi)) err = CDR_LOAD_E_UUID;
         } else {
           cdr_signal_info& g = x.rec;
-          g.initiated_id = C.key[r];
-          if (!parse_uuid(rd, x.uu, &g.signal_request_lo, &g.signal_request_hi)) err = CDR_LOAD_E_UUID;
+          if constexpr (!CQL) {
+            g.initiated_id = C.key[r];
+            if (!parse_uuid(rd, x.uu, &g.signal_request_lo, &g.signal_request_hi)) err = CDR_LOAD_E_UUID;
+          }
           if (err == CDR_DEC_OK) {
             g.signal_name = H(x.sp[0]);
             g.input = H(x.sp[1]);
@@ -387,6 +669,9 @@ __global__ __launch_bounds__(CDR_LOAD_BLOCK) void k_rows(LCtx C) {
       if (P == COUNT) {
         C.status[r] = err;
         if (err != CDR_DEC_OK) atomicMin(&C.fail[w], fail_word(TBL, r - umin32(C.row0[w], r), err));
+        if constexpr (CQL && TBL == 0) {
+          if (err != CDR_DEC_OK) C.gneed[r] = 0;
+        }
       }
       if (P == FILL) {
         const uint32_t d = C.dest[r];
@@ -1129,24 +1414,102 @@ __global__ __launch_bounds__(256) void k_gather_copy(const uint64_t* str_ref, co
   for (uint32_t i = lane; i < len; i += 64) dst[i] = src[i];
 }
 
+// ---------------------------------------------------------------- the Cassandra maps' split
+// One lane per (entry, table) walks its column: the count word, then pair after pair
+// delimited by the two length words alone.  The first launch counts the pairs (the rows) and
+// lowers the entry's failure word at a map-level finding; after one scan per table the second
+// writes each row's offset — its key's length word — at the entry's rows, and the end of the
+// table's last pair at [n_rows].
+struct QCtx {
+  const uint8_t* bytes;
+  uint64_t total;
+  const uint64_t* col_off[CDR_LOAD_TABLES];
+  uint32_t n_entries;
+  uint32_t* cnt;               // [5][n_entries + 1], the last of each zero
+  const uint32_t* row0;        // their exclusive scans
+  unsigned long long* fail;    // [n_entries]
+  uint64_t* off[CDR_LOAD_TABLES];  // WRITE: [n_rows[t] + 1]
+  uint32_t n_rows[CDR_LOAD_TABLES];
+};
+template <bool WRITE>
+__global__ __launch_bounds__(256) void k_cql_split(QCtx Q) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (uint64_t)CDR_LOAD_TABLES * Q.n_entries) return;
+  const uint32_t t = (uint32_t)(i / Q.n_entries), w = (uint32_t)(i % Q.n_entries);
+  const uint64_t slot = (uint64_t)t * (Q.n_entries + 1ull) + w;
+  const uint64_t* co = Q.col_off[0];
+#pragma unroll
+  for (uint32_t k = 1; k < CDR_LOAD_TABLES; k++) co = t == k ? Q.col_off[k] : co;
+  const uint64_t e = umin64(co[w + 1], Q.total), p = umin64(co[w], e);
+  uint32_t rows = 0, lo = 0, cap = 0;
+  uint64_t* off = nullptr;
+  if (WRITE) {  // every write capped by the entry's row range
+    uint32_t nr = Q.n_rows[0];
+    off = Q.off[0];
+#pragma unroll
+    for (uint32_t k = 1; k < CDR_LOAD_TABLES; k++) {
+      nr = t == k ? Q.n_rows[k] : nr;
+      off = t == k ? Q.off[k] : off;
+    }
+    lo = umin32(Q.row0[slot], nr);
+    cap = umin32(Q.row0[slot + 1], nr) - lo;
+    if (cap == 0) return;
+  }
+  int32_t finding = CDR_DEC_OK;
+  Rd r;
+  r.init(Q.bytes, p, e, Q.total);
+  if (e != p) {  // (an empty range: a null column, an empty map)
+    const int32_t n = (int32_t)r.be32();
+    if (!r.ok()) finding = r.err;
+    else if (n < 0) finding = CDR_DEC_BAD_SIZE;
+    else if ((uint32_t)n > CDR_LOAD_MAX_ENTRY_ROWS) finding = CDR_LOAD_E_ENTRY_ROWS;
+    const uint32_t want = finding ? 0u : WRITE ? umin32((uint32_t)n, cap) : (uint32_t)n;
+    while (rows < want) {
+      const uint64_t at = r.pos;
+      cq_delimit(r);
+      cq_delimit(r);
+      if (!r.ok()) {
+        finding = r.err;
+        break;
+      }
+      if (WRITE) off[lo + rows] = at;
+      rows++;
+    }
+  }
+  if (WRITE) {
+    uint32_t nr = Q.n_rows[0];
+#pragma unroll
+    for (uint32_t k = 1; k < CDR_LOAD_TABLES; k++) nr = t == k ? Q.n_rows[k] : nr;
+    if (rows == cap && lo + cap == nr) off[nr] = r.pos;  // the table's last row ends here
+  } else {
+    Q.cnt[slot] = rows;
+    if (finding != CDR_DEC_OK) atomicMin(&Q.fail[w], fail_word(t, rows, finding));
+  }
+}
+
 template <class T>
 int ws(cdr_ctx* c, int slot, uint64_t n, T** p) {
   *p = (T*)cdr_ws_get(c, slot, n * sizeof(T) + 8);
   return *p ? CDR_API_OK : CDR_API_ENOMEM;
 }
 
-template <int P>
-void launch_rows(int t, const LCtx& C, hipStream_t st) {
-  if (!C.n_rows) return;
+template <int P, bool CQL>
+void launch_rows_of(int t, const LCtx& C, hipStream_t st) {
   const dim3 grid((C.n_rows + CDR_LOAD_BLOCK - 1) / CDR_LOAD_BLOCK), blk(CDR_LOAD_BLOCK);
   const size_t lds = (CDR_LOAD_BLOCK / 64) * CDR_LOAD_STAGE;
   switch (t) {
-    case 0: hipLaunchKernelGGL((k_rows<0, P>), grid, blk, lds, st, C); break;
-    case 1: hipLaunchKernelGGL((k_rows<1, P>), grid, blk, lds, st, C); break;
-    case 2: hipLaunchKernelGGL((k_rows<2, P>), grid, blk, lds, st, C); break;
-    case 3: hipLaunchKernelGGL((k_rows<3, P>), grid, blk, lds, st, C); break;
-    default: hipLaunchKernelGGL((k_rows<4, P>), grid, blk, lds, st, C); break;
+    case 0: hipLaunchKernelGGL((k_rows<0, P, CQL>), grid, blk, lds, st, C); break;
+    case 1: hipLaunchKernelGGL((k_rows<1, P, CQL>), grid, blk, lds, st, C); break;
+    case 2: hipLaunchKernelGGL((k_rows<2, P, CQL>), grid, blk, lds, st, C); break;
+    case 3: hipLaunchKernelGGL((k_rows<3, P, CQL>), grid, blk, lds, st, C); break;
+    default: hipLaunchKernelGGL((k_rows<4, P, CQL>), grid, blk, lds, st, C); break;
   }
+}
+template <int P>
+void launch_rows(int t, const LCtx& C, hipStream_t st, bool cql) {
+  if (!C.n_rows) return;
+  if (cql) launch_rows_of<P, true>(t, C, st);
+  else launch_rows_of<P, false>(t, C, st);
 }
 
 template <int P>
@@ -1156,9 +1519,16 @@ void launch_exec(const XCtx& X, hipStream_t st) {
   hipLaunchKernelGGL((k_exec<P>), grid, blk, (CDR_LOAD_BLOCK / 64) * CDR_LOAD_STAGE, st, X);
 }
 
-// cdr_load_rows (xin == NULL) and cdr_load_state
+// what the Cassandra front end hands the passes besides a cdr_rows_in of generated offsets
+struct CqlX {
+  const unsigned long long* fail;  // [n_entries]: the split's map-level findings
+  int64_t* key;                    // [all rows]: in->key[t] point into it; the count pass writes
+  uint64_t *gneed, *goff;          // [n_rows[0] + 1]
+};
+
+// cdr_load_rows (xin == NULL) and cdr_load_state; cx != NULL: the passes of cdr_load_cql_rows
 int load_impl(cdr_ctx* ctx, const cdr_rows_in* in, const cdr_exec_rows_in* xin, cdr_rows_out* out,
-              cdr_state_out* xout, void* stream) {
+              cdr_state_out* xout, void* stream, const CqlX* cx = nullptr) {
   if (!ctx || !in || !out || !in->seed_off || in->n_seeds == 0) return CDR_API_EINVAL;
   if (xin && in->n_entries &&
       (!xin->blob_off || !xin->domain_id || !xin->run_id || !xin->workflow_id_off || !xin->next_event_id ||
@@ -1173,14 +1543,14 @@ int load_impl(cdr_ctx* ctx, const cdr_rows_in* in, const cdr_exec_rows_in* xin, 
     if (!in->blob_off[t] || !in->entry_row0[t] || (t != 1 && !in->key[t])) return CDR_API_EINVAL;
   }
   base[NT] = n_all;
-  if ((in->n_rows[1] && !in->timer_id_off) || (in->n_rows[0] && !in->act_heartbeat)) return CDR_API_EINVAL;
+  if (!cx && ((in->n_rows[1] && !in->timer_id_off) || (in->n_rows[0] && !in->act_heartbeat))) return CDR_API_EINVAL;
   if (n_all && (!in->n_entries || (in->n_bytes && !in->bytes))) return CDR_API_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   HIPCHK(hipSetDevice(cdr_ctx_device(ctx)));
   const uint32_t ne = in->n_entries;
   *out = cdr_rows_out{};
-  // every row belongs to an entry: entry_row0 runs from 0 to n_rows
-  {
+  // every row belongs to an entry: entry_row0 runs from 0 to n_rows (the split's own do)
+  if (!cx) {
     uint32_t ends[NT][2] = {};
     for (int t = 0; t < NT; t++) {
       if (!in->n_rows[t]) continue;
@@ -1193,7 +1563,7 @@ int load_impl(cdr_ctx* ctx, const cdr_rows_in* in, const cdr_exec_rows_in* xin, 
   }
   for (hipEvent_t& e : ctx->ld_ev)
     if (!e) HIPCHK(hipEventCreate(&e));
-  HIPCHK(hipEventRecord(ctx->ld_ev[0], st));
+  if (!cx) HIPCHK(hipEventRecord(ctx->ld_ev[0], st));  // (the split is part of the first pass)
   int rc;
   uint32_t *row_entry, *dest, *misc;
   int32_t *status, *estatus;
@@ -1245,6 +1615,7 @@ int load_impl(cdr_ctx* ctx, const cdr_rows_in* in, const cdr_exec_rows_in* xin, 
   unsigned long long* n_fields = reinterpret_cast<unsigned long long*>(misc) + 2;
   HIPCHK(hipMemsetAsync(misc, 0, 64, st));
   HIPCHK(hipMemsetAsync(fail, 0xFF, (2ull * ne + 1) * 8, st));
+  if (cx && ne) HIPCHK(hipMemcpyAsync(fail, cx->fail, 8ull * ne, hipMemcpyDeviceToDevice, st));
   HIPCHK(hipMemsetAsync(dest, 0xFF, (n_all + 1) * 4, st));
   LCtx C[NT];
   for (int t = 0; t < NT; t++) {
@@ -1266,13 +1637,30 @@ int load_impl(cdr_ctx* ctx, const cdr_rows_in* in, const cdr_exec_rows_in* xin, 
     c.tkey = tkey;
     c.n_rows = in->n_rows[t];
     c.n_entries = ne;
+    if (cx) {
+      c.key_out = cx->key + base[t];
+      c.gneed = cx->gneed;
+      c.goff = cx->goff;
+      c.gen_base = (uint64_t)GEN_BYTES * in->n_rows[2];
+    }
     if (c.n_rows)
       hipLaunchKernelGGL(k_row_entry, grid(c.n_rows), blk, 0, st, c.row0, ne, c.n_rows, row_entry + base[t]);
   }
   HIPCHK(hipGetLastError());
   // ---- pass 1: statuses and string-field counts
-  for (int t = 0; t < NT; t++) launch_rows<COUNT>(t, C[t], st);
+  const bool cql = cx != nullptr;
+  for (int t = 0; t < NT; t++) launch_rows<COUNT>(t, C[t], st, cql);
   XCnt xtot{{0, 0, 0, 0}};
+  if (cx && in->n_rows[0]) {  // the activity rows' list bodies in gen_bytes, scanned into offsets
+    const int n = (int)(in->n_rows[0] + 1);
+    HIPCHK(hipMemsetAsync(cx->gneed + in->n_rows[0], 0, 8, st));
+    size_t tb = 0;
+    HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, cx->gneed, cx->goff, n, st));
+    void* tmp = cdr_ws_get(ctx, WS_LD_XTMP, tb ? tb : 8);
+    if (!tmp) return CDR_API_ENOMEM;
+    HIPCHK(hipcub::DeviceScan::ExclusiveSum(tmp, tb, cx->gneed, cx->goff, n, st));
+    HIPCHK(hipMemcpyAsync(&xtot.v[3], cx->goff + in->n_rows[0], 8, hipMemcpyDeviceToHost, st));
+  }
   if (with_exec) {  // ... and the execution rows' item counts and gen_bytes need, scanned into offsets
     X.totals = n_fields;
     launch_exec<COUNT>(X, st);
@@ -1311,7 +1699,7 @@ int load_impl(cdr_ctx* ctx, const cdr_rows_in* in, const cdr_exec_rows_in* xin, 
   hipLaunchKernelGGL(k_seed, grid(in->n_seeds), blk, 0, st, T, in->seed_bytes, in->seed_off, in->n_seeds);
   for (int t = 0; t < NT; t++) {
     C[t].T = T;
-    launch_rows<INTERN>(t, C[t], st);
+    launch_rows<INTERN>(t, C[t], st, cql);
   }
   if (with_exec) {
     X.T = T;
@@ -1373,7 +1761,7 @@ int load_impl(cdr_ctx* ctx, const cdr_rows_in* in, const cdr_exec_rows_in* xin, 
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(ctx->ld_ev[3], st));
   // ---- pass 4: the records, then the entries
-  for (int t = 0; t < NT; t++) launch_rows<FILL>(t, C[t], st);
+  for (int t = 0; t < NT; t++) launch_rows<FILL>(t, C[t], st, cql);
   EpiIn E{};
   for (int t = 0; t < NT; t++) {
     E.row0[t] = in->entry_row0[t];
@@ -1433,6 +1821,88 @@ extern "C" int cdr_load_state(cdr_ctx* ctx, const cdr_rows_in* rows, const cdr_e
   if (!out) return CDR_API_EINVAL;
   *out = cdr_state_out{};
   return load_impl(ctx, rows, exec, &out->rows, out, stream);
+}
+
+extern "C" int cdr_load_cql_rows(cdr_ctx* ctx, const cdr_cql_rows_in* in, cdr_cql_rows_out* out, void* stream) {
+  if (!ctx || !in || !out || !in->seed_off || in->n_seeds == 0) return CDR_API_EINVAL;
+  constexpr int NT = CDR_LOAD_TABLES;
+  const uint32_t ne = in->n_entries;
+  if ((in->n_bytes && !in->bytes) || in->n_bytes >= (1ull << 35)) return CDR_API_EINVAL;
+  for (int t = 0; t < NT; t++)
+    if (ne && !in->col_off[t]) return CDR_API_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(hipSetDevice(cdr_ctx_device(ctx)));
+  *out = cdr_cql_rows_out{};
+  for (hipEvent_t& e : ctx->ld_ev)
+    if (!e) HIPCHK(hipEventCreate(&e));
+  HIPCHK(hipEventRecord(ctx->ld_ev[0], st));
+  int rc;
+  QCtx Q{};
+  uint32_t *cnt, *row0;
+  const uint64_t per = ne + 1ull;
+  if ((rc = ws(ctx, WS_LD_CQ_CNT, NT * per, &cnt)) || (rc = ws(ctx, WS_LD_CQ_ROW0, NT * per, &row0)) ||
+      (rc = ws(ctx, WS_LD_CQ_FAIL, per, &Q.fail)))
+    return rc;
+  Q.bytes = in->bytes;
+  Q.total = in->n_bytes;
+  for (int t = 0; t < NT; t++) Q.col_off[t] = in->col_off[t];
+  Q.n_entries = ne;
+  Q.cnt = cnt;
+  Q.row0 = row0;
+  uint32_t n_rows[NT] = {};
+  const dim3 blk(256), grid((uint32_t)((NT * (uint64_t)ne + 255) / 256));
+  if (ne) {
+    HIPCHK(hipMemsetAsync(cnt, 0, NT * per * 4, st));
+    HIPCHK(hipMemsetAsync(Q.fail, 0xFF, per * 8, st));
+    hipLaunchKernelGGL(k_cql_split<false>, grid, blk, 0, st, Q);
+    HIPCHK(hipGetLastError());
+    size_t tb = 0;
+    HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, cnt, row0, (int)per, st));
+    void* tmp = cdr_ws_get(ctx, WS_LD_XTMP, tb ? tb : 8);
+    if (!tmp) return CDR_API_ENOMEM;
+    for (int t = 0; t < NT; t++) {
+      HIPCHK(hipcub::DeviceScan::ExclusiveSum(tmp, tb, cnt + t * per, row0 + t * per, (int)per, st));
+      HIPCHK(hipMemcpyAsync(&n_rows[t], row0 + t * per + ne, 4, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));  // the one readback the split adds: the five row totals
+  }
+  uint64_t n_all = 0, base[NT];
+  for (int t = 0; t < NT; t++) {
+    base[t] = n_all;
+    n_all += n_rows[t];
+  }
+  uint64_t* off;
+  CqlX cx{};
+  cx.fail = Q.fail;
+  if ((rc = ws(ctx, WS_LD_CQ_OFF, n_all + NT, &off)) || (rc = ws(ctx, WS_LD_CQ_KEY, n_all + 1, &cx.key)) ||
+      (rc = ws(ctx, WS_LD_CQ_GNEED, n_rows[0] + 1ull, &cx.gneed)) ||
+      (rc = ws(ctx, WS_LD_CQ_GOFF, n_rows[0] + 1ull, &cx.goff)))
+    return rc;
+  cdr_rows_in R{};
+  R.bytes = in->bytes;
+  R.n_bytes = in->n_bytes;
+  R.seed_bytes = in->seed_bytes;
+  R.seed_off = in->seed_off;
+  R.n_entries = ne;
+  R.n_seeds = in->n_seeds;
+  for (int t = 0; t < NT; t++) {
+    Q.off[t] = off + base[t] + t;
+    Q.n_rows[t] = n_rows[t];
+    R.blob_off[t] = Q.off[t];
+    R.entry_row0[t] = row0 + t * per;
+    R.key[t] = cx.key + base[t];
+    R.n_rows[t] = n_rows[t];
+  }
+  if (n_all) {
+    hipLaunchKernelGGL(k_cql_split<true>, grid, blk, 0, st, Q);
+    HIPCHK(hipGetLastError());
+  }
+  if ((rc = load_impl(ctx, &R, nullptr, &out->rows, nullptr, stream, &cx))) return rc;
+  for (int t = 0; t < NT; t++) {
+    out->n_rows[t] = n_rows[t];
+    out->entry_row0[t] = row0 + t * per;
+  }
+  return CDR_API_OK;
 }
 
 extern "C" int cdr_load_pass_ms(cdr_ctx* ctx, float* ms) {

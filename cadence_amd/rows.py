@@ -8,7 +8,9 @@ cdr_exec_rows_in); ``load`` decodes the pending tables of a ``Rows`` on the devi
 returning host copies of every output; ``to_carry`` turns a decode into an ``engine.Carry``
 a batch can replay onto — a ``load_state`` result as it is, a ``load`` result with the
 caller's exec / repl / vh / rp / sa records.  ``gather`` runs cdr_strtab_gather_async on
-any decoded string table.
+any decoded string table.  The Cassandra form of the pending tables (cdr_load_cql_rows):
+``encode_state_cql`` wraps the CQL encoder's rows as map columns (a ``CqlCols``, built by
+``pack_cql``) and ``load_cql`` decodes them on the device into the same ``Loaded``.
 """
 from __future__ import annotations
 
@@ -295,6 +297,9 @@ class Loaded:
     persist: C.Array = None
     builder: np.ndarray = None      # uint32 [n_entries]
     exec_status: np.ndarray = None  # int32 [n_entries]
+    # load_cql: the rows the device split the map columns into
+    n_rows: list = None             # 5 counts
+    entry_row0: list = None         # 5 x uint32 [n_entries + 1]
 
     def rows(self, w: int, t: str):
         off = getattr(self.caps[w], t + "_off")
@@ -512,3 +517,149 @@ def to_carry(loaded: Loaded, other: engine.Outputs = None, src=None) -> engine.C
     if src is None:
         src = np.array([w if st.result[w].code == abi.OK else -1 for w in range(n)], np.int32)
     return engine.Carry(src=np.asarray(src, np.int32), state=st)
+
+
+# ---------------------------------------------------------------- the Cassandra form
+# (cdr.h cdr_load_cql_rows) A row's bound values, as cdr_encode_cql_async emits them, are the
+# map key and then the UDT's fields in the statement's order; a column Cassandra returns holds
+# each UDT's fields in the order the schema declares them.  Position i of the declared UDT is
+# statement field CQL_DECLARED[t][i] (tables not named: the orders agree).
+CQL_DECLARED = {"cancel": (0, 2, 1, 3), "signal": (0, 2, 1, 3, 4, 5, 6)}
+
+
+@dataclasses.dataclass
+class CqlCols:
+    """cdr_cql_rows_in on the host: entry w's column body of table t is
+    bytes[col_off[t][w]:col_off[t][w+1]] (empty: a null column)."""
+    bytes: np.ndarray    # uint8
+    col_off: list        # 5 x uint64 [n_entries + 1]
+    n_entries: int
+    src: list = None     # encode_state_cql: 5 x [(entry, row j of the entry)] per pair, in column order
+
+    def column(self, t: int, w: int) -> bytes:
+        return self.bytes[int(self.col_off[t][w]):int(self.col_off[t][w + 1])].tobytes()
+
+
+def cql_values(b: bytes) -> list:
+    """The [bytes] values (length words included) a run of CQL values consists of."""
+    out, p = [], 0
+    while p < len(b):
+        n = struct.unpack_from(">i", b, p)[0]
+        q = p + 4 + max(n, 0)
+        if q > len(b):
+            raise ValueError("a CQL value runs past its row")
+        out.append(b[p:q])
+        p = q
+    return out
+
+
+def cql_pair(table: str, values: bytes) -> bytes:
+    """One map pair from a row's bound values: the key, then the UDT value with its fields in
+    declaration order."""
+    v = cql_values(values)
+    key, f = v[0], v[1:]
+    perm = CQL_DECLARED.get(table)
+    if perm is not None:
+        f = [f[i] for i in perm]
+    udt = b"".join(f)
+    return key + struct.pack(">i", len(udt)) + udt
+
+
+def cql_column(pairs) -> bytes:
+    """A map column's body from its pairs; None: a null column."""
+    return b"" if pairs is None else struct.pack(">i", len(pairs)) + b"".join(pairs)
+
+
+def pack_cql(n_entries: int, cols) -> CqlCols:
+    """cols[t][w] = entry w's column body of table t (b"": null).  The buffer is table-major:
+    a table's columns lie one after another, so the rows a wavefront takes are one byte range."""
+    chunks, pos, offs = [], 0, []
+    for t in range(5):
+        off = [pos]
+        for w in range(n_entries):
+            chunks.append(bytes(cols[t][w]))
+            pos += len(cols[t][w])
+            off.append(pos)
+        offs.append(np.array(off, np.uint64))
+    data = np.frombuffer(b"".join(chunks) or b"\0", np.uint8).copy()
+    return CqlCols(data[:pos], offs, n_entries)
+
+
+def encode_state_cql(eng: engine.Engine, batch: engine.Batch, out: engine.Outputs, strings: list) -> CqlCols:
+    """The five pending tables of the OK entries of `out` as the Cassandra persistence returns
+    them: the device encoder's values (cdr_encode_cql_async) with each row's fields put into
+    declaration order, wrapped as map columns.  A row the encoder refuses is left out of its
+    map; an entry without rows in a table gets a null column.  `.src[t]` names each pair's
+    (entry, row of the entry)."""
+    cols, src = [], []
+    for t in TABLES:
+        got, codes = eng.encode_blobs(batch, out, t, strings, form="cql")
+        per, s = [], []
+        for w in range(batch.n_wfs):
+            pairs = []
+            if out.result[w].code == abi.OK:
+                base = getattr(out.plan.caps[w], t + "_off")
+                for j in range(len(out.rows(w, t))):
+                    if base + j in got and codes[base + j] == 0:
+                        pairs.append(cql_pair(t, got[base + j]))
+                        s.append((w, j))
+            per.append(cql_column(pairs or None))
+        cols.append(per)
+        src.append(s)
+    res = pack_cql(batch.n_wfs, cols)
+    res.src = src
+    return res
+
+
+def load_cql(eng: engine.Engine, cols: CqlCols, seeds: list, at_end: bool = False, check: bool = True,
+             n_bytes: int = None) -> Loaded:
+    """cdr_load_cql_rows on the device; host copies of every output, as `load` — with
+    .n_rows and .entry_row0 (5 x uint32 [n_entries + 1]), the rows the device found.
+    `n_bytes` overrides the buffer's length as the call is told it (offsets may lie past it)."""
+    L = abi.lib()
+    dev = DeviceBuffers()
+    try:
+        sb, so = string_table(seeds)
+        nb = len(cols.bytes) if n_bytes is None else n_bytes
+        buf = cols.bytes[:nb]
+        inp = abi.CdrCqlRowsIn()
+        inp.bytes = dev.up(buf if len(buf) else np.zeros(1, np.uint8), at_end and len(buf) > 0)
+        inp.n_bytes = nb
+        for t in range(5):
+            inp.col_off[t] = dev.up(cols.col_off[t])
+        inp.seed_bytes, inp.seed_off = dev.up(sb), dev.up(so)
+        inp.n_entries, inp.n_seeds = cols.n_entries, len(seeds)
+        cout = abi.CdrCqlRowsOut()
+        rc = L.cdr_load_cql_rows(eng.ctx, C.byref(inp), C.byref(cout), None)
+        if rc:
+            if check:
+                raise RuntimeError(f"cdr_load_cql_rows rc={rc}")
+            return Loaded({}, None, None, abi.CdrTotals(), [], np.zeros(0, np.int32), [], None, None, b"", 0, rc=rc)
+        out, ne = cout.rows, cols.n_entries
+        n_rows = [int(n) for n in cout.n_rows]
+
+        def recs(ptr, ty, n):
+            raw = dev.down(ptr, np.uint8, n * C.sizeof(ty)).tobytes()
+            return (ty * n).from_buffer_copy(raw) if n else (ty * 0)()
+        tables = {t: recs(getattr(out.state, t), engine.TABLE_TYPES[t], n_rows[i]) for i, t in enumerate(TABLES)}
+        result = recs(out.state.result, abi.CdrWfResult, ne)
+        caps = recs(out.caps, abi.CdrWfCaps, ne)
+        status = [dev.down(out.row_status[t], np.int32, n_rows[t]) for t in range(5)]
+        est = dev.down(out.entry_status, np.int32, ne)
+        ref = dev.down(out.str_ref, np.uint64, out.n_strings)
+        ln = dev.down(out.str_len, np.uint32, out.n_strings)
+        gen = dev.down(out.gen_bytes, np.uint8, out.n_gen_bytes).tobytes()
+        raw, sraw = buf.tobytes(), sb.tobytes()
+        strings = []
+        for h in range(out.n_strings):
+            r, n = int(ref[h]), int(ln[h])
+            s = sraw if r & abi.STR_REF_SEED else gen if r & abi.STR_REF_GEN else raw
+            r &= abi.STR_REF_GEN - 1
+            strings.append(s[r:r + n])
+        res = Loaded(tables, result, caps, out.totals, status, est, strings, ref, ln, gen, out.n_bad_entries)
+        res.n_rows = n_rows
+        res.entry_row0 = [dev.down(cout.entry_row0[t], np.uint32, ne + 1) if ne else np.zeros(1, np.uint32)
+                          for t in range(5)]
+        return res
+    finally:
+        dev.free()

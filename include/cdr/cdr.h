@@ -870,8 +870,9 @@ int cdr_plan_ndc_apply(const cdr_batch* b, const cdr_wf_caps* state_caps, cdr_wf
  * the encoders: 0 activity, 1 timer, 2 child, 3 request-cancel, 4 signal.
  * cdr_load_rows decodes these five tables alone (the caller supplies the exec / repl / vh / rp /
  * sa records); cdr_load_state below decodes the execution row with them.
- * OUT OF SCOPE of both: the Cassandra form, BufferedEvents, SignalRequestedIDs and the
- * execution row's CompletionEvent.
+ * The Cassandra form of the five pending tables is cdr_load_cql_rows further below.
+ * OUT OF SCOPE of all three: the Cassandra form of the execution row, BufferedEvents,
+ * SignalRequestedIDs and the execution row's CompletionEvent.
  *
  * Blob format.  A blob is a bare thriftrw binary-protocol struct with no 0x59 preamble
  * (blob.go:61-84).  The wire rules are those of cdr/ingest.h: fields in any order, unknown
@@ -1112,7 +1113,124 @@ typedef struct cdr_state_out { /* device buffers owned by the context */
 int cdr_load_state(cdr_ctx* ctx, const cdr_rows_in* rows, const cdr_exec_rows_in* exec, cdr_state_out* out,
                    void* stream);
 
-/* Device milliseconds of the last cdr_load_rows / cdr_load_state on the context, between HIP events on its
+/* The five pending tables from the Cassandra persistence: the map columns activity_map,
+ * timer_map, child_executions_map, request_cancel_map and signal_map as GetWorkflowExecution
+ * selects them (common/persistence/cassandra/cassandraPersistence.go:1228-1320, the maps at
+ * :1277-1316, templateGetWorkflowExecutionQuery :408), through createActivityInfo,
+ * createTimerInfo, createChildExecutionInfo, createRequestCancelInfo and createSignalInfo
+ * (cassandraPersistenceUtil.go:2055-2251).  Everything after the wire is cdr_load_rows: the
+ * same records, interning (seeds first, then hash rank), ascending key order,
+ * CDR_LOAD_E_DUP_KEY, per-entry failure rule (lowest table, then lowest row; CDR_E_LOAD_ROWS;
+ * other entries unaffected), str_ref bits 62 / 63, output lifetime and workspace.  The
+ * execution row (the execution / replication_state UDTs, version_histories, next_event_id) is
+ * not read: the caller supplies exec / repl / vh / rp / sa as with cdr_load_rows.
+ *
+ * Inputs (device pointers).  One byte buffer bytes[n_bytes]; per table t (0 activity .. 4
+ * signal) col_off[t] holds n_entries + 1 non-decreasing offsets, and entry w's column value
+ * BODY is bytes[col_off[t][w], col_off[t][w+1]) — without the column's own 4-byte length.
+ * Offsets are clamped to n_bytes; no byte outside [bytes, bytes + n_bytes) is read, whatever
+ * the counts and lengths inside say.  An empty range is a null column: an empty map.  Seeds as
+ * in cdr_rows_in.
+ *
+ * Wire.  A body is what Cassandra returns for map<K, frozen<udt>> (CQL native protocol v4): a
+ * big-endian int32 count n, then n pairs of [bytes] values (int32 length, -1 = null, then the
+ * bytes), the key and then the UDT value; the UDT value's body is its fields' [bytes] in the
+ * DECLARATION order of schema/cassandra/cadence/schema.cql:149-228 (not the statement order
+ * cdr_encode_cql_async emits: request_cancel_info and signal_info declare
+ * initiated_event_batch_id before initiated_id).  gocql is not vendored in the reference: the
+ * rules below are this contract's, restated in tests/cql_rows_ref.py.
+ *   The device splits the maps (the caller does not know row counts): a pre-pass, one lane per
+ *   (entry, table), reads the count and delimits the pairs; one scan per table gives
+ *   entry_row0[t]; one host readback of the five row totals sizes the workspace.  A row is a
+ *   delimited pair; row statuses exist for rows only.
+ *   Map-level findings.  A column of 1..3 bytes is CDR_DEC_TRUNCATED; a negative count is
+ *   CDR_DEC_BAD_SIZE; a count above CDR_LOAD_MAX_ENTRY_ROWS is CDR_LOAD_E_ENTRY_ROWS, decided from
+ *   the count word alone before any pair is walked (the column then has no rows).  A key or UDT
+ *   length below -1 is CDR_DEC_BAD_SIZE, a key or UDT that runs past its column (or whose
+ *   length word does) is CDR_DEC_TRUNCATED.  A map-level finding belongs to the index of the
+ *   first pair that could not be delimited (0 for the three count findings): pairs before it
+ *   are rows with statuses of their own, nothing after it is a row, and the finding takes part
+ *   in the entry's first-failure order as a row of that index would.  Bytes after the n-th
+ *   pair are ignored.  The map key is delimited and otherwise not read (keys come from the
+ *   UDT's own field, as in the reference).  A null UDT value is a UDT with no fields.
+ *   Fields.  A UDT value with fewer fields than declared leaves the missing trailing fields
+ *   null; bytes after the last declared field, inside the UDT's length, are ignored (a later
+ *   schema appends fields).  A field's length word or value that runs past its UDT is
+ *   CDR_DEC_TRUNCATED; a negative length other than -1 is CDR_DEC_BAD_SIZE.
+ *   Fixed-size values (bigint 8, int 4, boolean 1, double 8, uuid 16, timestamp 8 bytes): a null
+ *   or zero-length value is the type's zero (0, false, sixteen zero bytes, Go's zero time);
+ *   any other length that is not the type's size is CDR_LOAD_E_CQL_SIZE.  A boolean is true iff
+ *   its byte is non-zero.  Null or empty text / blob is "" (handle 0).
+ *   Timestamps are milliseconds: nanoseconds = ms * 1,000,000, a product outside int64 is
+ *   CDR_LOAD_E_SHAPE; Go's zero time is CDR_ZERO_TIME_NANOS.
+ *   list<text> (non_retriable_errors): null or empty value, or count 0: handle 0.  A value of
+ *   1..3 bytes, or an element that runs past the value, is CDR_DEC_TRUNCATED; a negative count,
+ *   a null element or another negative element length is CDR_DEC_BAD_SIZE.  A non-empty list is
+ *   interned under the project's convention, the thrift list body 0B + count + elements: the
+ *   CQL value's bytes up to the end of its last element are that body without the type byte,
+ *   so the body is written into gen_bytes and interned from there.
+ *   A row's status is its first finding in field order (a wrong size, an overflowing timestamp
+ *   and a wire error alike); the request-cancel ID's text is checked after the walk.
+ *
+ * Field mapping (every field not named is parsed over and dropped: the event blobs, details,
+ * started_identity, last_failure_*, last_worker_identity, event_data_encoding — the set the
+ * SQL loader drops):
+ *   activity_info -> cdr_activity_info one for one: version, schedule_id (the key),
+ *     scheduled_event_batch_id, scheduled_time, started_id, started_time, activity_id,
+ *     request_id, schedule_to_start / schedule_to_close / start_to_close / heart_beat timeouts
+ *     -> s2s / s2c / stc / hb, cancel_requested, cancel_request_id (the bigint),
+ *     last_hb_updated_time, timer_task_status, attempt, task_list, has_retry_policy,
+ *     init_interval, backoff_coefficient (the bits), max_interval, expiration_time,
+ *     max_attempts, non_retriable_errors.  From the nanosecond values on, the time and flag
+ *     rules are exactly cdr_load_rows's: CDR_AI_STARTED_TIME_SET iff started_time !=
+ *     CDR_ZERO_TIME_NANOS (then the value is kept, else 0); last_heartbeat_time is
+ *     last_hb_updated_time if != CDR_ZERO_TIME_NANOS, else 0, and CDR_AI_HEARTBEAT_TIME_SET iff
+ *     it is non-zero and STARTED is not set.  scheduled_time and expiration_time keep their
+ *     nanoseconds as they are (a null one is CDR_ZERO_TIME_NANOS).
+ *   timer_info: version, timer_id (text: the interned handle, and the key), started_id,
+ *     expiry_time (nanoseconds as they are), task_id.
+ *   child_execution_info: version, initiated_id (the key), initiated_event_batch_id, started_id,
+ *     started_workflow_id, started_run_id, create_request_id (uuid: create_request_hi = its
+ *     first 8 bytes, lo = its last 8), domain_name, workflow_type_name, parent_close_policy.
+ *     started_run_id is rendered as canonical lowercase text into gen_bytes and interned, as in
+ *     the SQL loader; sixteen zero bytes and the writer's emptyRunID
+ *     (30000000-0000-f000-f000-000000000000, cassandraPersistence.go:48, written at
+ *     cassandraPersistenceUtil.go:1461) both give handle 0.  The reference keeps the sentinel's
+ *     text there and nothing reads it before ReplicateChildWorkflowExecutionStartedEvent
+ *     overwrites it; with 0 a loaded row equals a replayed one (the decision cdr_load_state
+ *     documents for initiated_id).
+ *   request_cancel_info: version, initiated_event_batch_id, initiated_id (the key),
+ *     cancel_request_id (text: only the canonical 36-character form, else CDR_LOAD_E_UUID).
+ *   signal_info: version, initiated_event_batch_id, initiated_id (the key), signal_request_id
+ *     (uuid -> hi / lo), signal_name, input, control (null or empty: handle 0).
+ *
+ * Outputs: a cdr_rows_out exactly as cdr_load_rows fills it, over the discovered rows —
+ * n_rows[t] and entry_row0[t] (device, [n_entries + 1]) say which; row_status[t] has n_rows[t]
+ * words, rows in column order.  gen_bytes holds the child rows' run-ID texts first (36 bytes
+ * at 36 * the child row's index), then the activity rows' list bodies.  Synchronous on
+ * `stream`; one host round trip more than cdr_load_rows (the row totals); no allocation once
+ * the workspace is warm.  CDR_API_EINVAL for null arguments, n_seeds == 0, a null col_off[t]
+ * with n_entries != 0, null bytes with n_bytes != 0, and n_bytes >= 2^35 (row indices are 32
+ * bits and a pair takes at least 8 bytes). */
+#define CDR_LOAD_E_CQL_SIZE 22 /* a fixed-size CQL value whose length is neither 0 nor its type's size */
+typedef struct cdr_cql_rows_in { /* device pointers */
+  const uint8_t* bytes;
+  uint64_t n_bytes;
+  const uint64_t* col_off[CDR_LOAD_TABLES]; /* [n_entries + 1] */
+  const uint8_t* seed_bytes;
+  const uint64_t* seed_off;                 /* [n_seeds + 1]; seed 0 must be "" */
+  uint32_t n_entries, n_seeds;
+} cdr_cql_rows_in;
+typedef struct cdr_cql_rows_out { /* device buffers owned by the context */
+  cdr_rows_out rows;
+  uint32_t* entry_row0[CDR_LOAD_TABLES]; /* [n_entries + 1], device */
+  uint32_t n_rows[CDR_LOAD_TABLES];
+  uint32_t _pad;
+} cdr_cql_rows_out;
+int cdr_load_cql_rows(cdr_ctx* ctx, const cdr_cql_rows_in* in, cdr_cql_rows_out* out, void* stream);
+
+/* Device milliseconds of the last cdr_load_rows / cdr_load_state / cdr_load_cql_rows on the context
+ * (the map split of cdr_load_cql_rows counts into ms[0]), between HIP events on its
  * stream: ms[0] the count pass (with the row -> entry map), ms[1] the intern pass and the
  * string ranking (with the two host round trips that size the table and the sort), ms[2] the
  * row ranking, ms[3] the fill pass and the entry epilogue.  The call is synchronous and holds

@@ -22,6 +22,13 @@ base population's history blobs, tiled up to --ingest-bytes, in the same process
 Writes one JSON record (--out).
 
     python tools/load_bench.py --out profiles/load_rows.json
+
+--form cql measures the Cassandra form instead (cdr_load_cql_rows): the same four populations
+(configs 3 and 5, shared and distinct timer IDs) as map columns, each beside cdr_load_rows on
+the same states' SQL rows in the same process — the yardstick — with the ratio per population
+and per pass.  The map split counts into the first pass.
+
+    python tools/load_bench.py --form cql --out profiles/load_cql.json
 """
 import argparse
 import ctypes as C
@@ -168,6 +175,113 @@ def time_load(eng, R: rows.Rows, reps: int) -> dict:
     return rec
 
 
+def tile_cols(cols: rows.CqlCols, tile: int, timer_suffix: bool = False) -> rows.CqlCols:
+    """The map columns `tile` times over, table-major.  timer_suffix: every timer ID (the map
+    key and the UDT's field) gets its tiled entry's number appended, as distinct_timer_ids."""
+    import struct
+    segs, offs, pos = [], [], 0
+    n = cols.n_entries
+    for t in range(5):
+        o = cols.col_off[t]
+        if t == 1 and timer_suffix:
+            parts = []  # per base entry: [(id, version value, the fields after timer_id)]
+            for w in range(n):
+                body, rs = cols.column(1, w), []
+                if body:
+                    p = 4
+                    for _ in range(struct.unpack_from(">i", body, 0)[0]):
+                        kl = struct.unpack_from(">i", body, p)[0]
+                        ul = struct.unpack_from(">i", body, p + 4 + kl)[0]
+                        u = body[p + 8 + kl:p + 8 + kl + ul]
+                        il = struct.unpack_from(">i", u, 12)[0]
+                        rs.append((u[16:16 + il], u[:12], u[16 + il:]))
+                        p += 8 + kl + ul
+                parts.append(rs)
+            out, lens = [], np.zeros(n * tile + 1, np.uint64)
+            for e in range(n * tile):
+                rs = parts[e % n]
+                if rs:
+                    sfx = b"#%07d" % e
+                    col = [struct.pack(">i", len(rs))]
+                    for tid, ver, rest in rs:
+                        v = struct.pack(">i", len(tid) + len(sfx)) + tid + sfx
+                        col += [v, struct.pack(">i", len(ver) + len(v) + len(rest)), ver, v, rest]
+                    col = b"".join(col)
+                    out.append(col)
+                    lens[e + 1] = len(col)
+            seg = np.frombuffer(b"".join(out) or b"\0", np.uint8)[:int(lens.sum())]
+            offs.append(np.cumsum(lens).astype(np.uint64) + np.uint64(pos))
+            segs.append(seg)
+            pos += len(seg)
+            continue
+        seg = cols.bytes[int(o[0]):int(o[-1])]
+        offs.append(tile_offsets(o, tile, pos, np.uint64))
+        segs.append(np.tile(seg, tile))
+        pos += len(seg) * tile
+    return rows.CqlCols(np.concatenate(segs), offs, n * tile)
+
+
+def time_load_cql(eng, cols: rows.CqlCols, reps: int) -> dict:
+    """cdr_load_cql_rows over `cols` (seeds: "" alone), wall clock and passes."""
+    L = abi.lib()
+    n_bytes = int(len(cols.bytes))
+    dev = rows.DeviceBuffers()
+    try:
+        sb, so = ingest.string_table([b""])
+        inp = abi.CdrCqlRowsIn()
+        inp.bytes, inp.n_bytes = dev.up(cols.bytes), n_bytes
+        for t in range(5):
+            inp.col_off[t] = dev.up(cols.col_off[t])
+        inp.seed_bytes, inp.seed_off = dev.up(sb), dev.up(so)
+        inp.n_entries, inp.n_seeds = cols.n_entries, 1
+        wall, passes = [], [[] for _ in PASSES]
+        res = abi.CdrCqlRowsOut()
+        for rep in range(reps + 1):
+            assert dev.hip.hipDeviceSynchronize() == 0
+            t0 = time.perf_counter()
+            rc = L.cdr_load_cql_rows(eng.ctx, C.byref(inp), C.byref(res), None)
+            t1 = time.perf_counter()
+            assert rc == 0 and res.rows.n_bad_entries == 0, (rc, res.rows.n_bad_entries)
+            ms = (C.c_float * 4)()
+            assert L.cdr_load_pass_ms(eng.ctx, ms) == 0
+            if rep:  # the first call grows the workspace
+                wall.append(t1 - t0)
+                for i in range(4):
+                    passes[i].append(ms[i] / 1e3)
+        n_rows, n_strings = [int(x) for x in res.n_rows], int(res.rows.n_strings)
+    finally:
+        dev.free()
+    w = stats(wall)
+    rec = {"bytes": n_bytes, "strings": n_strings, "rows": dict(zip(rows.TABLES, n_rows)), "load_wall_s": w,
+           "load_gbs": n_bytes / w["median"] / 1e9, "load_rows_per_s": sum(n_rows) / w["median"], "passes": {}}
+    for name, xs in zip(PASSES, passes):
+        s = stats(xs)
+        rec["passes"][name] = {"s": s, "rows_per_s": sum(n_rows) / s["median"]}
+    return rec
+
+
+def versus(cql: dict, sql: dict) -> dict:
+    """cdr_load_cql_rows over cdr_load_rows on the same states: medians' ratios."""
+    return {"wall": cql["load_wall_s"]["median"] / sql["load_wall_s"]["median"], "bytes": cql["bytes"] / sql["bytes"],
+            "passes": {p: cql["passes"][p]["s"]["median"] / sql["passes"][p]["s"]["median"] for p in PASSES}}
+
+
+def bench_config_cql(eng, cfg: int, base: int, tile: int, reps: int) -> dict:
+    b = engine.synth_batch(cfg, base, seed=0x5EED0000 + cfg)
+    out = eng.replay(b)
+    strs = rows.state_strings(b, out)
+    R = tile_rows(rows.encode_state(eng, b, out, strs), tile)
+    cols = rows.encode_state_cql(eng, b, out, strs)
+    rec = {"config": cfg, "workflows": R.n_entries, "base_workflows": base, "tile": tile, "populations": {}}
+    for name, sql_rows, cql_cols in (("shared", R, tile_cols(cols, tile)),
+                                     ("distinct_timer_ids", distinct_timer_ids(R), tile_cols(cols, tile, True))):
+        sql = time_load(eng, sql_rows, reps)
+        cql = time_load_cql(eng, cql_cols, reps)
+        assert sum(cql["rows"].values()) == sum(sql_rows.n_rows) and cql["strings"] == sql["strings"]
+        rec["populations"][name] = {"load_rows": sql, "load_cql_rows": cql, "cql_over_sql": versus(cql, sql)}
+    return rec
+
+
 def added(state: dict, plain: dict) -> dict:
     """What the execution rows add to the call."""
     s = state["load_wall_s"]["median"] - plain["load_wall_s"]["median"]
@@ -241,6 +355,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--ingest-bytes", type=int, default=2_000_000_000)
     ap.add_argument("--out", default="")
+    ap.add_argument("--form", default="sql", choices=("sql", "cql"))
     args = ap.parse_args()
     try:
         import torch
@@ -252,9 +367,12 @@ def main():
            "build_flags": int(abi.lib().cdr_build_flags()), "reps": args.reps,
            "timing": "wall clock around the synchronous calls on a warm context (first call dropped); passes: HIP "
                      "events inside cdr_load_rows / cdr_load_state (the intern interval holds its two host round trips)",
-           "seeds": 1, "configs": []}
+           "seeds": 1, "form": args.form, "configs": []}
     for cfg in (int(c) for c in args.configs.split(",")):
-        r = bench_config(eng, cfg, args.base, args.tile, args.reps, args.ingest_bytes)
+        if args.form == "cql":
+            r = bench_config_cql(eng, cfg, args.base, args.tile, args.reps)
+        else:
+            r = bench_config(eng, cfg, args.base, args.tile, args.reps, args.ingest_bytes)
         rec["configs"].append(r)
         print(json.dumps(r), flush=True)
     eng.close()
