@@ -238,6 +238,12 @@ CdrCqlRowsIn = _S("cdr_cql_rows_in", [
     ("seed_off", C.c_void_p), ("n_entries", u32), ("n_seeds", u32)])
 CdrCqlRowsOut = _S("cdr_cql_rows_out", [
     ("rows", CdrRowsOut), ("entry_row0", C.c_void_p * LOAD_TABLES), ("n_rows", u32 * LOAD_TABLES), ("_pad", u32)])
+# whole stored states from Cassandra (cdr.h cdr_load_cql_state): the execution row's four columns
+CdrCqlExecIn = _S("cdr_cql_exec_in", [
+    ("execution_off", C.c_void_p), ("replication_state_off", C.c_void_p), ("version_histories_off", C.c_void_p),
+    ("vh_encoding_off", C.c_void_p), ("cluster_seed", u32 * MAX_CLUSTERS), ("n_clusters", u32), ("_pad", u32)])
+CdrCqlStateOut = _S("cdr_cql_state_out", [
+    ("rows", CdrCqlRowsOut), ("persist", C.c_void_p), ("builder", C.c_void_p), ("exec_status", C.c_void_p)])
 CdrOpts = _S("cdr_opts", [("plan_mode", u32), ("fast_path", i32), ("reg_path", i32), ("concurrent", i32),
                           ("workspace_bytes", u64)])
 CdrVHToken = _S("cdr_vh_token", [("tree", u32), ("_pad", u32), ("branch_lo", u64), ("branch_hi", u64)])
@@ -397,6 +403,7 @@ MIRRORS = {
     "cdr_rows_in": CdrRowsIn, "cdr_rows_out": CdrRowsOut,
     "cdr_exec_rows_in": CdrExecRowsIn, "cdr_state_out": CdrStateOut,
     "cdr_cql_rows_in": CdrCqlRowsIn, "cdr_cql_rows_out": CdrCqlRowsOut,
+    "cdr_cql_exec_in": CdrCqlExecIn, "cdr_cql_state_out": CdrCqlStateOut,
 }
 
 # C ABI entry points declared in include/cdr/cdr.h and include/cdr/synth.h
@@ -483,6 +490,8 @@ EXPORTS = {
     "cdr_load_state": (i32, [C.c_void_p, C.POINTER(CdrRowsIn), C.POINTER(CdrExecRowsIn), C.POINTER(CdrStateOut),
                              C.c_void_p]),
     "cdr_load_cql_rows": (i32, [C.c_void_p, C.POINTER(CdrCqlRowsIn), C.POINTER(CdrCqlRowsOut), C.c_void_p]),
+    "cdr_load_cql_state": (i32, [C.c_void_p, C.POINTER(CdrCqlRowsIn), C.POINTER(CdrCqlExecIn),
+                                 C.POINTER(CdrCqlStateOut), C.c_void_p]),
     "cdr_load_pass_ms": (i32, [C.c_void_p, C.POINTER(C.c_float)]),
     "cdr_strtab_gather_async": (i32, [C.c_void_p, C.c_void_p, C.c_void_p, u32, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -64,6 +64,8 @@ enum cdr_ws_slot {
   // cdr_load_cql_rows: the map split's pair counts, their scans (entry_row0), its failure words,
   // the generated row offsets and keys, and the activity rows' list-body sizes and offsets
   WS_LD_CQ_CNT, WS_LD_CQ_ROW0, WS_LD_CQ_FAIL, WS_LD_CQ_OFF, WS_LD_CQ_KEY, WS_LD_CQ_GNEED, WS_LD_CQ_GOFF,
+  // cdr_load_cql_state: the list-body scan's temporary storage (WS_LD_XTMP holds the execution rows' scan)
+  WS_LD_CQ_GTMP,
   WS_GATHER_TMP,  // cdr_strtab_gather_async: the offset scan's temporary storage
   WS_NUM
 };

@@ -1229,6 +1229,8 @@ uint64_t cdr_struct_size(const char* name) {
       {"cdr_state_out", sizeof(cdr_state_out)},
       {"cdr_cql_rows_in", sizeof(cdr_cql_rows_in)},
       {"cdr_cql_rows_out", sizeof(cdr_cql_rows_out)},
+      {"cdr_cql_exec_in", sizeof(cdr_cql_exec_in)},
+      {"cdr_cql_state_out", sizeof(cdr_cql_state_out)},
   };
   for (const E& e : table)
     if (std::strcmp(e.n, name) == 0) return e.s;

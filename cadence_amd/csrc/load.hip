@@ -25,11 +25,15 @@
 // a pair's UDT — a fixed sequence of length-prefixed values, straight-line code — into the same
 // record and Spans.  Keys come from the UDT (the count pass writes them out for the ranking),
 // and an activity's error list, whose bytes lack the thrift type byte, goes through gen_bytes.
+// Its execution row (cdr_load_cql_state) is the same front end of k_exec: XRow<true>::parse_cql
+// walks the `execution` UDT's declared fields, the replication_state and version_histories
+// columns are read beside it, and everything after the walk that reads the same bytes is shared.
 #include <hip/hip_runtime.h>
 
 #include <hipcub/hipcub.hpp>
 
 #include <cstdio>
+#include <type_traits>
 
 #include "cdr/cdr.h"
 #include "cdr/ingest.h"
@@ -283,6 +287,73 @@ __device__ __forceinline__ uint64_t list_hash(Rd& r, Span b, uint8_t* out) {
   }
   h = cdr_mix64(h ^ (n * 0x9E3779B97F4A7C15ull));
   return h ? h : 1u;
+}
+// a uuid: its 16 bytes; null or empty: none
+__device__ __forceinline__ Span cq_uuid(Rd& r) {
+  Span v;
+  return cq_fixed(r, 16, &v) ? v : Span{0, 0};
+}
+// a parent's ID: sixteen zero bytes and the writer's sentinel (x0000000-0000-f000-f000-000000000000,
+// `hi` its first 8 bytes) are none
+__device__ __forceinline__ Span cq_parent_uuid(Rd& r, uint64_t hi_none) {
+  const Span v = cq_uuid(r);
+  if (!v.n) return v;
+  const uint64_t hi = be64_at(r, v.at), lo = be64_at(r, v.at + 8);
+  const bool none = (hi == 0 && lo == 0) || (hi == hi_none && lo == 0xf000'000000000000ull);
+  return none ? Span{0, 0} : v;
+}
+// map<text, blob>: the value's bytes from its count to the end of its last pair and the count;
+// null, empty or count 0: none.  Every length is checked here, so a later walk of the pairs
+// stays inside the span.
+__device__ __forceinline__ Span cq_map_blob(Rd& r, uint32_t* n_pairs) {
+  *n_pairs = 0;
+  Span v;
+  if (!cq_val(r, &v) || v.n == 0) return Span{0, 0};
+  uint64_t p = v.at;
+  const uint64_t e = v.at + v.n;
+  if (e - p < 4) {
+    r.err = CDR_DEC_TRUNCATED;
+    return Span{0, 0};
+  }
+  const int32_t cnt = (int32_t)be32_at(r, p);
+  p += 4;
+  if (cnt < 0) {
+    r.err = CDR_DEC_BAD_SIZE;
+    return Span{0, 0};
+  }
+  for (int64_t k = 0; k < 2 * (int64_t)cnt; k++) {  // (each element takes 4 bytes at least: bounded by the value)
+    if (e - p < 4) {
+      r.err = CDR_DEC_TRUNCATED;
+      return Span{0, 0};
+    }
+    const int32_t len = (int32_t)be32_at(r, p);
+    p += 4;
+    if (len < 0) {  // a null element included
+      r.err = CDR_DEC_BAD_SIZE;
+      return Span{0, 0};
+    }
+    if (e - p < (uint64_t)len) {
+      r.err = CDR_DEC_TRUNCATED;
+      return Span{0, 0};
+    }
+    p += (uint64_t)len;
+  }
+  *n_pairs = (uint32_t)cnt;
+  return cnt ? Span{v.at, (uint32_t)(p - v.at)} : Span{0, 0};
+}
+// one [bytes] element of a collection the reader stands in: a missing one is truncation, a
+// null one an error unless `null_ok` (then it is empty)
+__device__ __forceinline__ void cq_elem(Rd& r, Span* v, bool null_ok) {
+  *v = Span{0, 0};
+  const int32_t len = (int32_t)r.be32();
+  if (!r.ok()) return;
+  if (len < 0) {
+    if (len != -1 || !null_ok) r.err = CDR_DEC_BAD_SIZE;
+    return;
+  }
+  if (!r.need((uint32_t)len)) return;
+  *v = Span{r.pos, (uint32_t)len};
+  r.pos += (uint32_t)len;
 }
 // one [bytes] of a map's pair delimited (the key, then the UDT): its length, -1 = null
 __device__ __forceinline__ int32_t cq_delimit(Rd& r) {
@@ -733,6 +804,8 @@ struct XCtx {
   cdr_reset_point* rp;
   cdr_kv* sa;
   uint32_t* n_sa;  // FILL: distinct search-attribute keys, for the epilogue
+  // the Cassandra form only (in.blob_off: the execution column's offsets)
+  const uint64_t *rs_off, *vhb_off, *vhe_off;  // replication_state, version_histories, its encoding
 };
 
 struct U16 {  // 16 bytes, big-endian
@@ -769,6 +842,23 @@ __device__ uint64_t memo_hash(Rd& r, Span m, uint8_t* out) {
   const uint64_t n = (uint64_t)m.n + 4;
   for (uint64_t i = 0; i < n; i++) {
     const uint32_t c = i == 0 ? 0x0Du : i == 2 ? 0x0Au : (i == 1 || i == n - 1) ? 0u : r.at(m.at + (i - 3));
+    h = (h ^ c) * 0x100000001B3ull;
+    if (out) out[i] = (uint8_t)c;
+  }
+  h = cdr_mix64(h ^ (n * 0x9E3779B97F4A7C15ull));
+  return h ? h : 1u;
+}
+
+// the Cassandra form's: 0D 00 0A 0B 0B, the CQL map body m (count and pairs), 00
+__device__ __forceinline__ uint64_t memo_hash_cql(Rd& r, Span m, uint8_t* out) {
+  uint64_t h = 0xCBF29CE484222325ull;
+  const uint64_t n = (uint64_t)m.n + 6;
+  for (uint64_t i = 0; i < n; i++) {
+    const uint32_t c = i == 0                        ? 0x0Du
+                       : i == 2                      ? 0x0Au
+                       : (i == 3 || i == 4)          ? 0x0Bu
+                       : (i == 1 || i == n - 1)      ? 0u
+                                                     : r.at(m.at + (i - 5));
     h = (h ^ c) * 0x100000001B3ull;
     if (out) out[i] = (uint8_t)c;
   }
@@ -847,13 +937,100 @@ __device__ int32_t parse_token(Rd& r, Span s, Tok* out) {
 
 enum : uint32_t { X_PARENT = 1, X_F18 = 2, X_F44 = 4, X_TOKEN = 8, X_SA = 16, X_MEMO = 32, X_VH = 64 };
 
-struct XRow {  // what the walk of one execution row leaves
+// the Cassandra form only: the IDs the SQL form has as key columns, the UDT's own event IDs,
+// the maps' pair counts
+struct XCqlOnly {
+  Span dom, run, wid;
+  int64_t next_ev, letid;
+  uint32_t n_sam, n_memo;
+};
+struct XSqlOnly {};
+
+template <bool CQL>
+struct XRow : std::conditional<CQL, XCqlOnly, XSqlOnly>::type {  // what the walk of one execution row leaves
   cdr_exec_info x;
   cdr_exec_persist ps;
   int64_t f44, f80, f82, f94, f106;
   uint32_t has;
   Span pdom, pwf, prun, tl, wt, ctx, crq, drq, stl, nonret, cron, token, clv, cfv, cimpl;
   Span rpb, rpenc, vhb, vhenc, lri, sam, memo;
+
+  // The Cassandra form: r stands at the first field of the `execution` UDT value and ends
+  // with it.  The 58 fields in declaration order (schema.cql:23-82), one bounded [bytes]
+  // read each; the first finding stops the walk (every later read gives the type's zero).
+  __device__ __forceinline__ void parse_cql(Rd& r) {
+    {
+      uint64_t* z = reinterpret_cast<uint64_t*>(&x);
+#pragma unroll
+      for (uint32_t i = 0; i < sizeof(x) / 8; i++) z[i] = 0;
+      z = reinterpret_cast<uint64_t*>(&ps);
+#pragma unroll
+      for (uint32_t i = 0; i < sizeof(ps) / 8; i++) z[i] = 0;
+    }
+    f44 = 0;
+    lri = vhb = vhenc = Span{0, 0};
+    this->dom = cq_uuid(r);
+    this->wid = cq_text(r);
+    this->run = cq_uuid(r);
+    pdom = cq_parent_uuid(r, 0x10000000'0000'f000ull);  // emptyDomainID
+    pwf = cq_text(r);
+    prun = cq_parent_uuid(r, 0x30000000'0000'f000ull);  // emptyRunID
+    x.initiated_id = cq_i64(r);
+    x.completion_event_batch_id = cq_i64(r);
+    cq_text(r);  // completion_event
+    cq_text(r);  // completion_event_data_encoding
+    tl = cq_text(r);
+    wt = cq_text(r);
+    x.workflow_timeout = cq_i32(r);
+    x.decision_timeout_value = cq_i32(r);
+    ctx = cq_text(r);
+    x.state = cq_i32(r);
+    x.close_status = cq_i32(r);
+    x.last_processed_event = cq_i64(r);
+    ps.start_time = cq_time(r);
+    ps.last_updated_time = cq_time(r);
+    crq = cq_uuid(r);
+    x.decision_version = cq_i64(r);
+    x.decision_schedule_id = cq_i64(r);
+    x.decision_started_id = cq_i64(r);
+    drq = cq_text(r);
+    x.decision_timeout = cq_i32(r);
+    x.decision_attempt = cq_i64(r);
+    x.decision_started_ts = cq_i64(r);
+    x.decision_scheduled_ts = cq_i64(r);
+    x.decision_original_scheduled_ts = cq_i64(r);
+    x.flags |= cq_bool(r, CDR_XI_CANCEL_REQUESTED);
+    cq_text(r);  // cancel_request_id
+    stl = cq_text(r);
+    f80 = cq_i32(r);
+    clv = cq_text(r);
+    cfv = cq_text(r);
+    cimpl = cq_text(r);
+    f82 = cq_i32(r);
+    x.flags |= cq_bool(r, CDR_XI_HAS_RETRY);
+    x.initial_interval = cq_i32(r);
+    x.backoff_coefficient = __longlong_as_double((long long)cq_i64(r));
+    x.maximum_interval = cq_i32(r);
+    f94 = cq_time(r);
+    x.maximum_attempts = cq_i32(r);
+    nonret = cq_list_text(r);
+    cq_i32(r);  // event_store_version
+    f106 = cq_i32(r);
+    token = cq_text(r);
+    ps.history_size = cq_i64(r);
+    x.last_first_event_id = cq_i64(r);
+    this->next_ev = cq_i64(r);
+    cron = cq_text(r);
+    x.expiration_seconds = cq_i32(r);
+    this->letid = cq_i64(r);
+    rpb = cq_text(r);
+    rpenc = cq_text(r);
+    sam = cq_map_blob(r, &this->n_sam);
+    memo = cq_map_blob(r, &this->n_memo);
+    // a parent that is none with the writer's emptyInitiatedID: what a replay leaves (cdr.h)
+    if (!pdom.n && x.initiated_id == -7) x.initiated_id = CDR_EMPTY_EVENT_ID;
+    has = X_PARENT | X_F18 | (token.n ? X_TOKEN : 0u) | (sam.n ? X_SA : 0u) | (memo.n ? X_MEMO : 0u);
+  }
 
   __device__ __forceinline__ void parse(Rd& r) {
     {
@@ -950,7 +1127,7 @@ __device__ __forceinline__ void store_whole(T* dst, const T& v) {
   for (uint32_t i = 0; i < sizeof(T) / 8; i++) o[i] = s[i];
 }
 
-template <int P>
+template <int P, bool CQL>
 __global__ __launch_bounds__(CDR_LOAD_BLOCK) void k_exec(XCtx C) {
   const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
@@ -970,8 +1147,19 @@ __global__ __launch_bounds__(CDR_LOAD_BLOCK) void k_exec(XCtx C) {
     rd.sb = (const LDS3 uint8_t*)stage;
     rd.s_lo = s_lo;
     rd.s_n = s_n;
-    XRow R;
-    R.parse(rd);
+    XRow<CQL> R;
+    if constexpr (CQL) {  // the other three columns are small: read through the window
+      R.parse_cql(rd);
+      uint64_t e2 = umin64(C.vhb_off[w + 1], C.total), p2 = umin64(C.vhb_off[w], e2);
+      R.vhb = Span{p2, (uint32_t)(e2 - p2)};
+      e2 = umin64(C.vhe_off[w + 1], C.total), p2 = umin64(C.vhe_off[w], e2);
+      R.vhenc = Span{p2, (uint32_t)(e2 - p2)};
+      e2 = umin64(C.rs_off[w + 1], C.total), p2 = umin64(C.rs_off[w], e2);
+      R.lri = Span{p2, (uint32_t)(e2 - p2)};  // the replication_state body
+      R.has |= (R.lri.n ? X_F44 : 0u) | (R.vhb.n ? X_VH : 0u);
+    } else {
+      R.parse(rd);
+    }
     int32_t err = rd.err;
     // ---- the status, the builder and the item lists, derived alike in every pass
     uint32_t builder = CDR_BUILDER_LOCAL;
@@ -990,44 +1178,99 @@ __global__ __launch_bounds__(CDR_LOAD_BLOCK) void k_exec(XCtx C) {
       R.x.initiated_id = CDR_EMPTY_EVENT_ID;
     }
     if (!err && ((R.pdom.n != 0 && R.pdom.n != 16) || (R.prun.n != 0 && R.prun.n != 16))) err = CDR_LOAD_E_UUID;
+    bool unknown_cluster = false;
+    if constexpr (CQL) {
+      // replication_state: current_version, start_version, last_write_version,
+      // last_write_event_id, last_replication_info (schema.cql:91-97); its wire findings
+      if (!err && (R.has & X_F44)) {
+        Rd q = sub_reader(rd, R.lri.at, R.lri.n);
+        rs.current_version = cq_i64(q);
+        rs.start_version = cq_i64(q);
+        rs.last_write_version = cq_i64(q);
+        rs.last_write_event_id = cq_i64(q);
+        Span m;
+        if (cq_val(q, &m) && m.n) {
+          Rd mq = sub_reader(q, m.at, m.n);
+          const int32_t cnt = (int32_t)mq.be32();
+          if (mq.ok() && cnt < 0) mq.err = CDR_DEC_BAD_SIZE;
+          for (int32_t k = 0; k < cnt && mq.ok(); k++) {  // (8 bytes a pair at least: bounded by the value)
+            Span key, u;
+            cq_elem(mq, &key, false);
+            cq_elem(mq, &u, true);
+            if (!mq.ok()) break;
+            Rd uq = sub_reader(mq, u.at, u.n);  // replication_info{version, last_event_id}
+            const int64_t ver = cq_i64(uq), last = cq_i64(uq);
+            if (uq.err) {
+              mq.err = uq.err;
+              break;
+            }
+            uint32_t ci = CDR_MAX_CLUSTERS;
+            for (uint32_t i = 0; i < C.in.n_clusters && ci == CDR_MAX_CLUSTERS; i++) {
+              const uint32_t s = C.in.cluster_seed[i];
+              if (s >= C.n_seeds) continue;
+              const uint64_t a = C.seed_off[s], n = C.seed_off[s + 1] - a;
+              if (n != key.n) continue;
+              bool same = true;
+              for (uint32_t j = 0; j < key.n && same; j++) same = rd.at(key.at + j) == C.seed_bytes[a + j];
+              if (same) ci = i;
+            }
+            if (ci == CDR_MAX_CLUSTERS) {
+              unknown_cluster = true;
+            } else {
+              rs.lri_mask |= 1u << ci;
+              rs.lri_version[ci] = ver;
+              rs.lri_last_event_id[ci] = last;
+            }
+          }
+          if (mq.err) q.err = mq.err;
+        }
+        err = q.err;
+      }
+    }
     if (!err && (R.has & X_F44) && (R.has & X_VH)) err = CDR_LOAD_E_SHAPE;
     if (!err && (R.has & X_F44)) {
       builder = CDR_BUILDER_2DC;
       rs.present = 1;
-      rs.start_version = R.ps.start_version;
-      rs.current_version = R.ps.current_version;
-      rs.last_write_version = C.in.last_write_version[w];
-      rs.last_write_event_id = R.f44;
-      if (R.lri.n >= 6 && rd.at(R.lri.at) == T_STRING && rd.at(R.lri.at + 1) == T_STRUCT) {
-        Rd q = sub_reader(rd, R.lri.at + 2, R.lri.n - 2);
-        const uint32_t cnt = (uint32_t)q.size();
-        for (uint32_t k = 0; k < cnt && q.ok() && !err; k++) {
-          Span key{0, 0};
-          f_str(q, T_STRING, &key);
-          int64_t ver = 0, last = 0;
-          fields(q, [&](uint32_t t, uint32_t id) {
-            switch (id) {
-              case 10: f_i64(q, t, &ver); break;
-              case 12: f_i64(q, t, &last); break;
-              default: skip1(q, t); break;
+      if constexpr (CQL) {
+        R.ps.start_version = rs.start_version;
+        R.ps.current_version = rs.current_version;
+        if (unknown_cluster) err = CDR_LOAD_E_CLUSTER;
+      } else {
+        rs.start_version = R.ps.start_version;
+        rs.current_version = R.ps.current_version;
+        rs.last_write_version = C.in.last_write_version[w];
+        rs.last_write_event_id = R.f44;
+        if (R.lri.n >= 6 && rd.at(R.lri.at) == T_STRING && rd.at(R.lri.at + 1) == T_STRUCT) {
+          Rd q = sub_reader(rd, R.lri.at + 2, R.lri.n - 2);
+          const uint32_t cnt = (uint32_t)q.size();
+          for (uint32_t k = 0; k < cnt && q.ok() && !err; k++) {
+            Span key{0, 0};
+            f_str(q, T_STRING, &key);
+            int64_t ver = 0, last = 0;
+            fields(q, [&](uint32_t t, uint32_t id) {
+              switch (id) {
+                case 10: f_i64(q, t, &ver); break;
+                case 12: f_i64(q, t, &last); break;
+                default: skip1(q, t); break;
+              }
+            });
+            uint32_t ci = CDR_MAX_CLUSTERS;
+            for (uint32_t i = 0; i < C.in.n_clusters && ci == CDR_MAX_CLUSTERS; i++) {
+              const uint32_t s = C.in.cluster_seed[i];
+              if (s >= C.n_seeds) continue;
+              const uint64_t a = C.seed_off[s], n = C.seed_off[s + 1] - a;
+              if (n != key.n) continue;
+              bool same = true;
+              for (uint32_t j = 0; j < key.n && same; j++) same = rd.at(key.at + j) == C.seed_bytes[a + j];
+              if (same) ci = i;
             }
-          });
-          uint32_t ci = CDR_MAX_CLUSTERS;
-          for (uint32_t i = 0; i < C.in.n_clusters && ci == CDR_MAX_CLUSTERS; i++) {
-            const uint32_t s = C.in.cluster_seed[i];
-            if (s >= C.n_seeds) continue;
-            const uint64_t a = C.seed_off[s], n = C.seed_off[s + 1] - a;
-            if (n != key.n) continue;
-            bool same = true;
-            for (uint32_t j = 0; j < key.n && same; j++) same = rd.at(key.at + j) == C.seed_bytes[a + j];
-            if (same) ci = i;
-          }
-          if (ci == CDR_MAX_CLUSTERS) {
-            err = CDR_LOAD_E_CLUSTER;
-          } else {
-            rs.lri_mask |= 1u << ci;
-            rs.lri_version[ci] = ver;
-            rs.lri_last_event_id[ci] = last;
+            if (ci == CDR_MAX_CLUSTERS) {
+              err = CDR_LOAD_E_CLUSTER;
+            } else {
+              rs.lri_mask |= 1u << ci;
+              rs.lri_version[ci] = ver;
+              rs.lri_last_event_id[ci] = last;
+            }
           }
         }
       }
@@ -1051,7 +1294,10 @@ __global__ __launch_bounds__(CDR_LOAD_BLOCK) void k_exec(XCtx C) {
         if (!err && n_rp > CDR_LOAD_MAX_RESET_POINTS) err = CDR_LOAD_E_SHAPE;
       }
     }
-    if (!err && (R.has & X_SA)) {
+    if constexpr (CQL) {  // the pairs were delimited in the walk: the counts alone are left
+      n_sa = R.n_sam;
+      if (!err && (R.n_sam > CDR_LOAD_MAX_SEARCH_ATTR || R.n_memo > CDR_LOAD_MAX_SEARCH_ATTR)) err = CDR_LOAD_E_SHAPE;
+    } else if (!err && (R.has & X_SA)) {
       if (rd.at(R.sam.at) == T_STRING && rd.at(R.sam.at + 1) == T_STRING) {
         Rd q = sub_reader(rd, R.sam.at + 2, 4);
         n_sa = (uint32_t)q.size();
@@ -1135,35 +1381,58 @@ __global__ __launch_bounds__(CDR_LOAD_BLOCK) void k_exec(XCtx C) {
         return tab_lookup(C.T, h);
       };
       cdr_exec_info& x = R.x;
-      x.domain_id = G(u16_col(C.in.domain_id + 16ull * w));
-      x.run_id = G(u16_col(C.in.run_id + 16ull * w));
-      {
+      if constexpr (CQL) {  // (a null ID is sixteen zero bytes)
+        x.domain_id = G(R.dom.n ? u16_at(rd, R.dom.at) : U16{0, 0});
+        x.run_id = G(R.run.n ? u16_at(rd, R.run.at) : U16{0, 0});
+        x.workflow_id = H(R.wid);
+      } else {
+        x.domain_id = G(u16_col(C.in.domain_id + 16ull * w));
+        x.run_id = G(u16_col(C.in.run_id + 16ull * w));
         const uint64_t e2 = umin64(C.in.workflow_id_off[w + 1], C.total), p2 = umin64(C.in.workflow_id_off[w], e2);
         x.workflow_id = H(Span{p2, (uint32_t)(e2 - p2)});
       }
       x.parent_domain_id = R.pdom.n ? G(u16_at(rd, R.pdom.at)) : 0u;
       x.parent_run_id = R.prun.n ? G(u16_at(rd, R.prun.at)) : 0u;
       x.parent_workflow_id = H(R.pwf);
-      x.create_request_id = H(R.crq);
+      if constexpr (CQL) x.create_request_id = G(R.crq.n ? u16_at(rd, R.crq.at) : U16{0, 0});
+      else x.create_request_id = H(R.crq);
       x.task_list = H(R.tl);
       x.workflow_type = H(R.wt);
       x.cron_schedule = H(R.cron);
-      x.nonretriable = H(R.nonret);
+      if constexpr (CQL) {  // the list body gets its type byte in the entry's share of gen_bytes
+        if (R.nonret.n) {
+          const uint64_t n = (uint64_t)R.nonret.n + 1;
+          if (P == COUNT) {
+            n_str++;
+            need.v[3] += n;
+          } else if (P == INTERN) {
+            if (g + n <= o1.v[3]) {
+              const uint64_t h = list_hash(rd, R.nonret, C.gen + g);
+              tab_insert(C.T, h, (C.gen_base + g) | GEN_REF, (uint32_t)n, UNASSIGNED);
+            }
+            g += n;
+          } else {
+            x.nonretriable = tab_lookup(C.T, list_hash(rd, R.nonret, nullptr));
+          }
+        }
+      } else {
+        x.nonretriable = H(R.nonret);
+      }
       x.branch_tree_id = H(tok.tree);
       x.decision_request_id = H(R.drq);
       if (R.has & X_MEMO) {
-        const uint64_t n = (uint64_t)R.memo.n + 4;
+        const uint64_t n = (uint64_t)R.memo.n + (CQL ? 6 : 4);
         if (P == COUNT) {
           n_str++;
           need.v[3] += n;
         } else if (P == INTERN) {
           if (g + n <= o1.v[3]) {
-            const uint64_t h = memo_hash(rd, R.memo, C.gen + g);
+            const uint64_t h = CQL ? memo_hash_cql(rd, R.memo, C.gen + g) : memo_hash(rd, R.memo, C.gen + g);
             tab_insert(C.T, h, (C.gen_base + g) | GEN_REF, (uint32_t)n, UNASSIGNED);
           }
           g += n;
         } else {
-          x.memo = tab_lookup(C.T, memo_hash(rd, R.memo, nullptr));
+          x.memo = tab_lookup(C.T, CQL ? memo_hash_cql(rd, R.memo, nullptr) : memo_hash(rd, R.memo, nullptr));
         }
       }
       cdr_exec_persist& ps = R.ps;
@@ -1211,7 +1480,10 @@ __global__ __launch_bounds__(CDR_LOAD_BLOCK) void k_exec(XCtx C) {
       uint32_t n_keys = 0;
       {
         const uint64_t cap = umin64(n_sa, o1.v[2] - o0.v[2]);
-        Rd q = sub_reader(rd, R.sam.at + 6, R.sam.n >= 6 ? R.sam.n - 6 : 0);
+        // (past the map's header: the thrift type bytes and count, or the CQL count; a thrift
+        // binary and a CQL [bytes] element are both a big-endian length and the bytes)
+        constexpr uint32_t HDR = CQL ? 4 : 6;
+        Rd q = sub_reader(rd, R.sam.at + HDR, R.sam.n >= HDR ? R.sam.n - HDR : 0);
         cdr_kv* o = P == FILL ? C.sa + o0.v[2] : nullptr;
         for (uint64_t k = 0; k < cap && q.ok(); k++) {
           Span ks{0, 0}, vs{0, 0};
@@ -1249,8 +1521,13 @@ __global__ __launch_bounds__(CDR_LOAD_BLOCK) void k_exec(XCtx C) {
         x.attempt = (int32_t)(uint32_t)(uint64_t)R.f82;
         x.signal_count = (int32_t)(uint32_t)(uint64_t)R.f106;
         if (!(R.has & X_F18)) x.completion_event_batch_id = CDR_EMPTY_EVENT_ID;
-        x.next_event_id = C.in.next_event_id[w];
-        x.last_event_task_id = 0;
+        if constexpr (CQL) {  // the UDT's own (the Cassandra read assigns both)
+          x.next_event_id = R.next_ev;
+          x.last_event_task_id = R.letid;
+        } else {
+          x.next_event_id = C.in.next_event_id[w];
+          x.last_event_task_id = 0;
+        }
         x.flags |= CDR_XI_STARTED | ((R.has & X_TOKEN) ? CDR_XI_HAS_BRANCH : 0u) |
                    ((R.has & X_MEMO) ? CDR_XI_HAS_MEMO : 0u) | ((R.has & X_SA) ? CDR_XI_HAS_SEARCH_ATTR : 0u) |
                    (has_points ? CDR_XI_HAS_RESET_POINTS : 0u) | (vh_branch ? CDR_XI_VH_BRANCH : 0u);
@@ -1513,10 +1790,12 @@ void launch_rows(int t, const LCtx& C, hipStream_t st, bool cql) {
 }
 
 template <int P>
-void launch_exec(const XCtx& X, hipStream_t st) {
+void launch_exec(const XCtx& X, hipStream_t st, bool cql) {
   if (!X.n_entries) return;
   const dim3 grid((X.n_entries + CDR_LOAD_BLOCK - 1) / CDR_LOAD_BLOCK), blk(CDR_LOAD_BLOCK);
-  hipLaunchKernelGGL((k_exec<P>), grid, blk, (CDR_LOAD_BLOCK / 64) * CDR_LOAD_STAGE, st, X);
+  const size_t lds = (CDR_LOAD_BLOCK / 64) * CDR_LOAD_STAGE;
+  if (cql) hipLaunchKernelGGL((k_exec<P, true>), grid, blk, lds, st, X);
+  else hipLaunchKernelGGL((k_exec<P, false>), grid, blk, lds, st, X);
 }
 
 // what the Cassandra front end hands the passes besides a cdr_rows_in of generated offsets
@@ -1524,13 +1803,14 @@ struct CqlX {
   const unsigned long long* fail;  // [n_entries]: the split's map-level findings
   int64_t* key;                    // [all rows]: in->key[t] point into it; the count pass writes
   uint64_t *gneed, *goff;          // [n_rows[0] + 1]
+  const cdr_cql_exec_in* xq;       // cdr_load_cql_state: the execution row's columns (xin holds execution_off)
 };
 
 // cdr_load_rows (xin == NULL) and cdr_load_state; cx != NULL: the passes of cdr_load_cql_rows
 int load_impl(cdr_ctx* ctx, const cdr_rows_in* in, const cdr_exec_rows_in* xin, cdr_rows_out* out,
               cdr_state_out* xout, void* stream, const CqlX* cx = nullptr) {
   if (!ctx || !in || !out || !in->seed_off || in->n_seeds == 0) return CDR_API_EINVAL;
-  if (xin && in->n_entries &&
+  if (xin && !cx && in->n_entries &&
       (!xin->blob_off || !xin->domain_id || !xin->run_id || !xin->workflow_id_off || !xin->next_event_id ||
        !xin->last_write_version || xin->n_clusters > CDR_MAX_CLUSTERS || (in->n_bytes && !in->bytes)))
     return CDR_API_EINVAL;
@@ -1590,6 +1870,11 @@ int load_impl(cdr_ctx* ctx, const cdr_rows_in* in, const cdr_exec_rows_in* xin, 
     X.bytes = in->bytes;
     X.total = in->n_bytes;
     X.in = *xin;
+    if (cx) {
+      X.rs_off = cx->xq->replication_state_off;
+      X.vhb_off = cx->xq->version_histories_off;
+      X.vhe_off = cx->xq->vh_encoding_off;
+    }
     X.seed_bytes = in->seed_bytes;
     X.seed_off = in->seed_off;
     X.n_seeds = in->n_seeds;
@@ -1641,7 +1926,6 @@ int load_impl(cdr_ctx* ctx, const cdr_rows_in* in, const cdr_exec_rows_in* xin, 
       c.key_out = cx->key + base[t];
       c.gneed = cx->gneed;
       c.goff = cx->goff;
-      c.gen_base = (uint64_t)GEN_BYTES * in->n_rows[2];
     }
     if (c.n_rows)
       hipLaunchKernelGGL(k_row_entry, grid(c.n_rows), blk, 0, st, c.row0, ne, c.n_rows, row_entry + base[t]);
@@ -1651,19 +1935,20 @@ int load_impl(cdr_ctx* ctx, const cdr_rows_in* in, const cdr_exec_rows_in* xin, 
   const bool cql = cx != nullptr;
   for (int t = 0; t < NT; t++) launch_rows<COUNT>(t, C[t], st, cql);
   XCnt xtot{{0, 0, 0, 0}};
+  uint64_t act_gen = 0;  // the Cassandra form's activity list bodies: after the execution rows' shares
   if (cx && in->n_rows[0]) {  // the activity rows' list bodies in gen_bytes, scanned into offsets
     const int n = (int)(in->n_rows[0] + 1);
     HIPCHK(hipMemsetAsync(cx->gneed + in->n_rows[0], 0, 8, st));
     size_t tb = 0;
     HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, cx->gneed, cx->goff, n, st));
-    void* tmp = cdr_ws_get(ctx, WS_LD_XTMP, tb ? tb : 8);
+    void* tmp = cdr_ws_get(ctx, WS_LD_CQ_GTMP, tb ? tb : 8);
     if (!tmp) return CDR_API_ENOMEM;
     HIPCHK(hipcub::DeviceScan::ExclusiveSum(tmp, tb, cx->gneed, cx->goff, n, st));
-    HIPCHK(hipMemcpyAsync(&xtot.v[3], cx->goff + in->n_rows[0], 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&act_gen, cx->goff + in->n_rows[0], 8, hipMemcpyDeviceToHost, st));
   }
   if (with_exec) {  // ... and the execution rows' item counts and gen_bytes need, scanned into offsets
     X.totals = n_fields;
-    launch_exec<COUNT>(X, st);
+    launch_exec<COUNT>(X, st, cql);
     size_t tb = 0;
     HIPCHK(hipcub::DeviceScan::ExclusiveScan(nullptr, tb, X.cnt, xoff, XCntAdd(), XCnt{{0, 0, 0, 0}}, (int)(ne + 1), st));
     void* tmp = cdr_ws_get(ctx, WS_LD_XTMP, tb ? tb : 8);
@@ -1677,8 +1962,11 @@ int load_impl(cdr_ctx* ctx, const cdr_rows_in* in, const cdr_exec_rows_in* xin, 
   HIPCHK(hipMemcpyAsync(&n_str_fields, n_fields, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   const uint64_t gen_rows = (uint64_t)GEN_BYTES * in->n_rows[2];  // the child rows' part of gen_bytes
-  if ((rc = ws(ctx, WS_LD_GEN, gen_rows + xtot.v[3] + 8, &gen))) return rc;
-  for (int t = 0; t < NT; t++) C[t].gen = gen;
+  if ((rc = ws(ctx, WS_LD_GEN, gen_rows + xtot.v[3] + act_gen + 8, &gen))) return rc;
+  for (int t = 0; t < NT; t++) {
+    C[t].gen = gen;
+    C[t].gen_base = gen_rows + xtot.v[3];
+  }
   if (with_exec) {
     X.gen = gen + gen_rows;
     X.gen_base = gen_rows;
@@ -1703,7 +1991,7 @@ int load_impl(cdr_ctx* ctx, const cdr_rows_in* in, const cdr_exec_rows_in* xin, 
   }
   if (with_exec) {
     X.T = T;
-    launch_exec<INTERN>(X, st);
+    launch_exec<INTERN>(X, st, cql);
   }
   if (in->n_rows[2])
     hipLaunchKernelGGL(k_gen_intern, grid(in->n_rows[2]), blk, 0, st, T, gen, row_entry + base[2], fail,
@@ -1767,7 +2055,7 @@ int load_impl(cdr_ctx* ctx, const cdr_rows_in* in, const cdr_exec_rows_in* xin, 
     E.row0[t] = in->entry_row0[t];
     E.n_rows[t] = in->n_rows[t];
   }
-  if (with_exec) launch_exec<FILL>(X, st);
+  if (with_exec) launch_exec<FILL>(X, st, cql);
   if (ne)
     hipLaunchKernelGGL(k_epilogue, grid(ne), blk, 0, st, E, ne, fail, result, caps, estatus, misc + 2,
                        (const XCnt*)(with_exec ? xoff : nullptr), (const uint32_t*)n_sa);
@@ -1792,7 +2080,7 @@ int load_impl(cdr_ctx* ctx, const cdr_rows_in* in, const cdr_exec_rows_in* xin, 
   for (int t = 0; t < NT; t++) out->row_status[t] = status + base[t];
   out->entry_status = estatus;
   out->gen_bytes = gen;
-  out->n_gen_bytes = gen_rows + xtot.v[3];
+  out->n_gen_bytes = gen_rows + xtot.v[3] + act_gen;
   out->n_bad_entries = n_bad;
   if (with_exec) {
     out->state.exec = X.exec;
@@ -1823,8 +2111,15 @@ extern "C" int cdr_load_state(cdr_ctx* ctx, const cdr_rows_in* rows, const cdr_e
   return load_impl(ctx, rows, exec, &out->rows, out, stream);
 }
 
-extern "C" int cdr_load_cql_rows(cdr_ctx* ctx, const cdr_cql_rows_in* in, cdr_cql_rows_out* out, void* stream) {
+namespace {
+// cdr_load_cql_rows (xq == NULL) and cdr_load_cql_state
+int load_cql_impl(cdr_ctx* ctx, const cdr_cql_rows_in* in, const cdr_cql_exec_in* xq, cdr_cql_rows_out* out,
+                  cdr_state_out* xout, void* stream) {
   if (!ctx || !in || !out || !in->seed_off || in->n_seeds == 0) return CDR_API_EINVAL;
+  if (xq && in->n_entries &&
+      (!xq->execution_off || !xq->replication_state_off || !xq->version_histories_off || !xq->vh_encoding_off ||
+       xq->n_clusters > CDR_MAX_CLUSTERS))
+    return CDR_API_EINVAL;
   constexpr int NT = CDR_LOAD_TABLES;
   const uint32_t ne = in->n_entries;
   if ((in->n_bytes && !in->bytes) || in->n_bytes >= (1ull << 35)) return CDR_API_EINVAL;
@@ -1897,12 +2192,35 @@ extern "C" int cdr_load_cql_rows(cdr_ctx* ctx, const cdr_cql_rows_in* in, cdr_cq
     hipLaunchKernelGGL(k_cql_split<true>, grid, blk, 0, st, Q);
     HIPCHK(hipGetLastError());
   }
-  if ((rc = load_impl(ctx, &R, nullptr, &out->rows, nullptr, stream, &cx))) return rc;
+  cdr_exec_rows_in xin{};
+  if (xq) {  // the execution column is the rows' blob; the other columns go by cx.xq
+    xin.blob_off = xq->execution_off;
+    for (uint32_t i = 0; i < CDR_MAX_CLUSTERS; i++) xin.cluster_seed[i] = xq->cluster_seed[i];
+    xin.n_clusters = xq->n_clusters;
+    cx.xq = xq;
+  }
+  if ((rc = load_impl(ctx, &R, xq ? &xin : nullptr, &out->rows, xout, stream, &cx))) return rc;
   for (int t = 0; t < NT; t++) {
     out->n_rows[t] = n_rows[t];
     out->entry_row0[t] = row0 + t * per;
   }
   return CDR_API_OK;
+}
+}  // namespace
+
+extern "C" int cdr_load_cql_rows(cdr_ctx* ctx, const cdr_cql_rows_in* in, cdr_cql_rows_out* out, void* stream) {
+  return load_cql_impl(ctx, in, nullptr, out, nullptr, stream);
+}
+
+extern "C" int cdr_load_cql_state(cdr_ctx* ctx, const cdr_cql_rows_in* rows, const cdr_cql_exec_in* exec,
+                                  cdr_cql_state_out* out, void* stream) {
+  if (!out) return CDR_API_EINVAL;
+  cdr_state_out x{};
+  const int rc = load_cql_impl(ctx, rows, exec, &out->rows, &x, stream);
+  out->persist = x.persist;
+  out->builder = x.builder;
+  out->exec_status = x.exec_status;
+  return rc;
 }
 
 extern "C" int cdr_load_pass_ms(cdr_ctx* ctx, float* ms) {

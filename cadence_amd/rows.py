@@ -10,7 +10,10 @@ a batch can replay onto — a ``load_state`` result as it is, a ``load`` result 
 caller's exec / repl / vh / rp / sa records.  ``gather`` runs cdr_strtab_gather_async on
 any decoded string table.  The Cassandra form of the pending tables (cdr_load_cql_rows):
 ``encode_state_cql`` wraps the CQL encoder's rows as map columns (a ``CqlCols``, built by
-``pack_cql``) and ``load_cql`` decodes them on the device into the same ``Loaded``.
+``pack_cql``) and ``load_cql`` decodes them on the device into the same ``Loaded``; with
+``exec_rows=True`` the execution row's four columns go with them (a ``CqlExec``) and
+``load_cql_state`` decodes the whole state (cdr_load_cql_state), which ``to_carry`` takes as
+it takes a ``load_state`` result.
 """
 from __future__ import annotations
 
@@ -525,6 +528,45 @@ def to_carry(loaded: Loaded, other: engine.Outputs = None, src=None) -> engine.C
 # each UDT's fields in the order the schema declares them.  Position i of the declared UDT is
 # statement field CQL_DECLARED[t][i] (tables not named: the orders agree).
 CQL_DECLARED = {"cancel": (0, 2, 1, 3), "signal": (0, 2, 1, 3, 4, 5, 6)}
+# The execution row (cdr.h cdr_load_cql_state): the workflow_execution UDT's 58 fields in the
+# order the update statement binds them (cdr_encode_cql_async table 5), and in the order the
+# schema declares them; EXEC_DECLARED[i] is the statement field at declared position i.
+EXEC_STATEMENT = (
+    "domain_id", "workflow_id", "run_id", "parent_domain_id", "parent_workflow_id", "parent_run_id", "initiated_id",
+    "completion_event_batch_id", "completion_event", "completion_event_data_encoding", "task_list",
+    "workflow_type_name", "workflow_timeout", "decision_task_timeout", "execution_context", "state", "close_status",
+    "last_first_event_id", "last_event_task_id", "next_event_id", "last_processed_event", "start_time",
+    "last_updated_time", "create_request_id", "signal_count", "history_size", "decision_version",
+    "decision_schedule_id", "decision_started_id", "decision_request_id", "decision_timeout", "decision_attempt",
+    "decision_timestamp", "decision_scheduled_timestamp", "decision_original_scheduled_timestamp", "cancel_requested",
+    "cancel_request_id", "sticky_task_list", "sticky_schedule_to_start_timeout", "client_library_version",
+    "client_feature_version", "client_impl", "auto_reset_points", "auto_reset_points_encoding", "attempt",
+    "has_retry_policy", "init_interval", "backoff_coefficient", "max_interval", "expiration_time", "max_attempts",
+    "non_retriable_errors", "event_store_version", "branch_token", "cron_schedule", "expiration_seconds",
+    "search_attributes", "memo")
+EXEC_DECLARED_NAMES = (
+    "domain_id", "workflow_id", "run_id", "parent_domain_id", "parent_workflow_id", "parent_run_id", "initiated_id",
+    "completion_event_batch_id", "completion_event", "completion_event_data_encoding", "task_list",
+    "workflow_type_name", "workflow_timeout", "decision_task_timeout", "execution_context", "state", "close_status",
+    "last_processed_event", "start_time", "last_updated_time", "create_request_id", "decision_version",
+    "decision_schedule_id", "decision_started_id", "decision_request_id", "decision_timeout", "decision_attempt",
+    "decision_timestamp", "decision_scheduled_timestamp", "decision_original_scheduled_timestamp", "cancel_requested",
+    "cancel_request_id", "sticky_task_list", "sticky_schedule_to_start_timeout", "client_library_version",
+    "client_feature_version", "client_impl", "attempt", "has_retry_policy", "init_interval", "backoff_coefficient",
+    "max_interval", "expiration_time", "max_attempts", "non_retriable_errors", "event_store_version", "signal_count",
+    "branch_token", "history_size", "last_first_event_id", "next_event_id", "cron_schedule", "expiration_seconds",
+    "last_event_task_id", "auto_reset_points", "auto_reset_points_encoding", "search_attributes", "memo")
+EXEC_DECLARED = tuple(EXEC_STATEMENT.index(n) for n in EXEC_DECLARED_NAMES)
+assert sorted(EXEC_DECLARED) == list(range(58))
+EXEC_COLUMNS = ("execution", "replication_state", "version_histories", "version_histories_encoding")
+
+
+@dataclasses.dataclass
+class CqlExec:
+    """cdr_cql_exec_in on the host: entry w's body of column c (EXEC_COLUMNS) is
+    bytes[off[c][w]:off[c][w+1]] of the CqlCols that holds it (empty: null)."""
+    off: list           # 4 x uint64 [n_entries + 1]
+    cluster_seed: list  # seed index of cluster i's name
 
 
 @dataclasses.dataclass
@@ -535,9 +577,13 @@ class CqlCols:
     col_off: list        # 5 x uint64 [n_entries + 1]
     n_entries: int
     src: list = None     # encode_state_cql: 5 x [(entry, row j of the entry)] per pair, in column order
+    exec: CqlExec = None  # the execution row's columns (cdr_load_cql_state)
 
     def column(self, t: int, w: int) -> bytes:
         return self.bytes[int(self.col_off[t][w]):int(self.col_off[t][w + 1])].tobytes()
+
+    def exec_column(self, c: int, w: int) -> bytes:
+        return self.bytes[int(self.exec.off[c][w]):int(self.exec.off[c][w + 1])].tobytes()
 
 
 def cql_values(b: bytes) -> list:
@@ -570,27 +616,53 @@ def cql_column(pairs) -> bytes:
     return b"" if pairs is None else struct.pack(">i", len(pairs)) + b"".join(pairs)
 
 
-def pack_cql(n_entries: int, cols) -> CqlCols:
-    """cols[t][w] = entry w's column body of table t (b"": null).  The buffer is table-major:
-    a table's columns lie one after another, so the rows a wavefront takes are one byte range."""
+def cql_exec_columns(builder: int, values: bytes) -> tuple:
+    """The execution row's four column bodies (EXEC_COLUMNS) from the values its update
+    statement binds (cdr_encode_cql_async table 5): the UDT's 58 fields put into declaration
+    order; a 2DC row's replication tail wrapped as a replication_state body (its trailing
+    next_event_id column is the UDT's own); an NDC row's version_histories and encoding."""
+    v = cql_values(values)
+    f, tail = v[:58], v[58:]
+    assert len(f) == 58 and len(tail) == {abi.BUILDER_2DC: 6, abi.BUILDER_NDC: 3}.get(builder, 1)
+    execution = b"".join(f[i] for i in EXEC_DECLARED)
+    if builder == abi.BUILDER_2DC:
+        return execution, b"".join(tail[:5]), b"", b""
+    if builder == abi.BUILDER_NDC:
+        return execution, b"", tail[1][4:], tail[2][4:]
+    return execution, b"", b"", b""
+
+
+def pack_cql(n_entries: int, cols, exec_cols=None, cluster_seed=()) -> CqlCols:
+    """cols[t][w] = entry w's column body of table t (b"": null).  The buffer is column-major:
+    a table's columns lie one after another, so the rows a wavefront takes are one byte range.
+    exec_cols[c][w] = entry w's body of the execution row's column c (EXEC_COLUMNS): the four
+    columns follow the tables, laid out the same way."""
     chunks, pos, offs = [], 0, []
-    for t in range(5):
+    for col in list(cols[:5]) + list(exec_cols or []):
         off = [pos]
         for w in range(n_entries):
-            chunks.append(bytes(cols[t][w]))
-            pos += len(cols[t][w])
+            chunks.append(bytes(col[w]))
+            pos += len(col[w])
             off.append(pos)
         offs.append(np.array(off, np.uint64))
     data = np.frombuffer(b"".join(chunks) or b"\0", np.uint8).copy()
-    return CqlCols(data[:pos], offs, n_entries)
+    res = CqlCols(data[:pos], offs[:5], n_entries)
+    if exec_cols is not None:
+        assert len(exec_cols) == 4
+        res.exec = CqlExec(offs[5:], list(cluster_seed))
+    return res
 
 
-def encode_state_cql(eng: engine.Engine, batch: engine.Batch, out: engine.Outputs, strings: list) -> CqlCols:
+def encode_state_cql(eng: engine.Engine, batch: engine.Batch, out: engine.Outputs, strings: list,
+                     exec_rows: bool = False, persist=None, cluster_names=None) -> CqlCols:
     """The five pending tables of the OK entries of `out` as the Cassandra persistence returns
     them: the device encoder's values (cdr_encode_cql_async) with each row's fields put into
     declaration order, wrapped as map columns.  A row the encoder refuses is left out of its
     map; an entry without rows in a table gets a null column.  `.src[t]` names each pair's
-    (entry, row of the entry)."""
+    (entry, row of the entry).
+    exec_rows=True adds the execution row's columns (cql_exec_columns of the encoder's table-5
+    values; `persist` and `cluster_names` as in encode_state); an entry that is not OK, or whose
+    row the encoder refuses, gets a one-byte execution body (it fails to load)."""
     cols, src = [], []
     for t in TABLES:
         got, codes = eng.encode_blobs(batch, out, t, strings, form="cql")
@@ -606,7 +678,19 @@ def encode_state_cql(eng: engine.Engine, batch: engine.Batch, out: engine.Output
             per.append(cql_column(pairs or None))
         cols.append(per)
         src.append(s)
-    res = pack_cql(batch.n_wfs, cols)
+    xcols = None
+    if exec_rows:
+        names = list(cluster_names if cluster_names is not None else [])
+        if persist is None:
+            persist = (abi.CdrExecPersist * max(1, batch.n_wfs))()
+        got, codes = eng.encode_blobs(batch, out, "exec", strings, persist, names, form="cql")
+        xcols = [[], [], [], []]
+        for w in range(batch.n_wfs):
+            ok = out.result[w].code == abi.OK and w in got and codes[w] == 0
+            four = cql_exec_columns(batch.wfs[w].builder, got[w]) if ok else (b"\0", b"", b"", b"")
+            for c in range(4):
+                xcols[c].append(four[c])
+    res = pack_cql(batch.n_wfs, cols, xcols, cluster_names or ())
     res.src = src
     return res
 
@@ -616,6 +700,18 @@ def load_cql(eng: engine.Engine, cols: CqlCols, seeds: list, at_end: bool = Fals
     """cdr_load_cql_rows on the device; host copies of every output, as `load` — with
     .n_rows and .entry_row0 (5 x uint32 [n_entries + 1]), the rows the device found.
     `n_bytes` overrides the buffer's length as the call is told it (offsets may lie past it)."""
+    return _load_cql(eng, cols, seeds, at_end, check, n_bytes, False)
+
+
+def load_cql_state(eng: engine.Engine, cols: CqlCols, seeds: list, at_end: bool = False, check: bool = True,
+                   n_bytes: int = None, cluster_seed=None) -> Loaded:
+    """cdr_load_cql_state on the device: as `load_cql`, with the execution rows of `cols.exec`
+    decoded too, the outputs `load_state` has (cols.exec None: exec == NULL, cdr_load_cql_rows'
+    results).  `cluster_seed` overrides cols.exec.cluster_seed."""
+    return _load_cql(eng, cols, seeds, at_end, check, n_bytes, True, cluster_seed)
+
+
+def _load_cql(eng, cols, seeds, at_end, check, n_bytes, state, cluster_seed=None) -> Loaded:
     L = abi.lib()
     dev = DeviceBuffers()
     try:
@@ -629,11 +725,26 @@ def load_cql(eng: engine.Engine, cols: CqlCols, seeds: list, at_end: bool = Fals
             inp.col_off[t] = dev.up(cols.col_off[t])
         inp.seed_bytes, inp.seed_off = dev.up(sb), dev.up(so)
         inp.n_entries, inp.n_seeds = cols.n_entries, len(seeds)
-        cout = abi.CdrCqlRowsOut()
-        rc = L.cdr_load_cql_rows(eng.ctx, C.byref(inp), C.byref(cout), None)
+        X = cols.exec if state else None
+        if state:
+            sout, xin = abi.CdrCqlStateOut(), None
+            if X is not None:
+                xin = abi.CdrCqlExecIn()
+                xin.execution_off, xin.replication_state_off = dev.up(X.off[0]), dev.up(X.off[1])
+                xin.version_histories_off, xin.vh_encoding_off = dev.up(X.off[2]), dev.up(X.off[3])
+                cs = list(X.cluster_seed if cluster_seed is None else cluster_seed)
+                xin.n_clusters = len(cs)
+                for i, h in enumerate(cs[:abi.MAX_CLUSTERS]):
+                    xin.cluster_seed[i] = h
+            rc = L.cdr_load_cql_state(eng.ctx, C.byref(inp), C.byref(xin) if xin is not None else None, C.byref(sout),
+                                      None)
+            cout = sout.rows
+        else:
+            cout = abi.CdrCqlRowsOut()
+            rc = L.cdr_load_cql_rows(eng.ctx, C.byref(inp), C.byref(cout), None)
         if rc:
             if check:
-                raise RuntimeError(f"cdr_load_cql_rows rc={rc}")
+                raise RuntimeError(f"cdr_load_cql_{'state' if state else 'rows'} rc={rc}")
             return Loaded({}, None, None, abi.CdrTotals(), [], np.zeros(0, np.int32), [], None, None, b"", 0, rc=rc)
         out, ne = cout.rows, cols.n_entries
         n_rows = [int(n) for n in cout.n_rows]
@@ -660,6 +771,14 @@ def load_cql(eng: engine.Engine, cols: CqlCols, seeds: list, at_end: bool = Fals
         res.n_rows = n_rows
         res.entry_row0 = [dev.down(cout.entry_row0[t], np.uint32, ne + 1) if ne else np.zeros(1, np.uint32)
                           for t in range(5)]
+        if X is not None:
+            for t in ("vh", "rp", "sa"):
+                tables[t] = recs(getattr(out.state, t), engine.TABLE_TYPES[t], getattr(out.totals, t))
+            res.exec = recs(out.state.exec, abi.CdrExecInfo, ne)
+            res.repl = recs(out.state.repl, abi.CdrReplState, ne)
+            res.persist = recs(sout.persist, abi.CdrExecPersist, ne)
+            res.builder = dev.down(sout.builder, np.uint32, ne)
+            res.exec_status = dev.down(sout.exec_status, np.int32, ne)
         return res
     finally:
         dev.free()

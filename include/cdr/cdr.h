@@ -1122,8 +1122,9 @@ int cdr_load_state(cdr_ctx* ctx, const cdr_rows_in* rows, const cdr_exec_rows_in
  * same records, interning (seeds first, then hash rank), ascending key order,
  * CDR_LOAD_E_DUP_KEY, per-entry failure rule (lowest table, then lowest row; CDR_E_LOAD_ROWS;
  * other entries unaffected), str_ref bits 62 / 63, output lifetime and workspace.  The
- * execution row (the execution / replication_state UDTs, version_histories, next_event_id) is
- * not read: the caller supplies exec / repl / vh / rp / sa as with cdr_load_rows.
+ * execution row (the execution / replication_state UDTs, version_histories) is not read
+ * here: cdr_load_cql_state below reads it in the same call; with this one the caller supplies
+ * exec / repl / vh / rp / sa as with cdr_load_rows.
  *
  * Inputs (device pointers).  One byte buffer bytes[n_bytes]; per table t (0 activity .. 4
  * signal) col_off[t] holds n_entries + 1 non-decreasing offsets, and entry w's column value
@@ -1229,8 +1230,104 @@ typedef struct cdr_cql_rows_out { /* device buffers owned by the context */
 } cdr_cql_rows_out;
 int cdr_load_cql_rows(cdr_ctx* ctx, const cdr_cql_rows_in* in, cdr_cql_rows_out* out, void* stream);
 
-/* Device milliseconds of the last cdr_load_rows / cdr_load_state / cdr_load_cql_rows on the context
- * (the map split of cdr_load_cql_rows counts into ms[0]), between HIP events on its
+/* Whole stored states from the Cassandra persistence: cdr_load_cql_rows with the execution row
+ * decoded too — the `execution` UDT, the `replication_state` UDT, `version_histories` and
+ * `version_histories_encoding` as GetWorkflowExecution selects them (cassandraPersistence.go:
+ * 1228-1332), through createWorkflowExecutionInfo (cassandraPersistenceUtil.go:1798-1935),
+ * createReplicationState (:1937-1966) and createReplicationInfo (:2472).  It relates to
+ * cdr_load_cql_rows as cdr_load_state relates to cdr_load_rows: exec == NULL is cdr_load_cql_rows
+ * (that call is this one with exec == NULL), and with exec the outputs are exactly
+ * cdr_load_state's — state.exec / repl / vh / rp / sa, caps, result counts, totals, persist,
+ * builder, exec_status — over one string table and one handle space, the pending tables filled
+ * as cdr_load_cql_rows fills them.  A failing execution row is table 5 in its entry's
+ * first-failure order.  No host round trip more than cdr_load_cql_rows and cdr_load_state make
+ * (the per-entry counts share their scan and readback); no allocation once the workspace is warm.
+ *
+ * Inputs (cdr_cql_exec_in, device pointers): four more columns in in->bytes, each [n_entries + 1]
+ * non-decreasing offsets clamped to n_bytes, entry w's column BODY (without its own 4-byte
+ * length) at [off[w], off[w+1]): the `execution` UDT value, the `replication_state` UDT value
+ * (empty: null), the `version_histories` blob (empty: null) and the
+ * `version_histories_encoding` text.  cluster_seed / n_clusters as in cdr_exec_rows_in.
+ *
+ * Wire.  The execution body holds the 58 fields of workflow_execution as [bytes] values in the
+ * DECLARATION order of schema.cql:23-82 — not the statement order cdr_encode_cql_async emits
+ * (last_first_event_id is the statement's 18th field and the declaration's 50th).  The rules are
+ * cdr_load_cql_rows': missing trailing fields are null, bytes after the last declared field are
+ * ignored, a null or empty fixed-size value is the type's zero and another wrong size is
+ * CDR_LOAD_E_CQL_SIZE (event_store_version, which is dropped, included), length errors are
+ * CDR_DEC_TRUNCATED / CDR_DEC_BAD_SIZE, timestamps are milliseconds x 1,000,000 (outside int64:
+ * CDR_LOAD_E_SHAPE; null: CDR_ZERO_TIME_NANOS).  Field mapping onto cdr_exec_info /
+ * cdr_exec_persist; where nothing is said the SQL loader's rule applies to the decoded value:
+ *   domain_id, run_id, create_request_id (uuid; null: sixteen zero bytes): canonical lowercase
+ *     text written into the entry's share of gen_bytes and interned from there (the SQL form
+ *     takes create_request_id as a plain string).  workflow_id: the UDT's text (the read has no
+ *     key columns).
+ *   parent_domain_id / parent_run_id: sixteen zero bytes and the writer's sentinels
+ *     emptyDomainID / emptyRunID (cassandraPersistence.go:46-48) give handle 0 (:1818, :1825);
+ *     parent_workflow_id and initiated_id as they are — but the writer's emptyInitiatedID (-7,
+ *     :69, stored for a workflow without a parent) under a parent domain that is none reads as
+ *     EmptyEventID (-23), what every replay leaves there, so that a loaded state equals a
+ *     replayed one (cdr_load_state's decision for the same field).
+ *   completion_event_batch_id, next_event_id and last_event_task_id are the UDT's values.
+ *     last_event_task_id is KEPT: the Cassandra read assigns it (:1856); cdr_load_state gives 0.
+ *   start_time, last_updated_time (timestamps), history_size, sticky_task_list,
+ *     sticky_schedule_to_start_timeout, client_library_version / client_feature_version /
+ *     client_impl and execution_context go to persist; attempt, signal_count and the sticky
+ *     timeout are CQL int (nothing is narrowed).
+ *   expiration_time: CDR_XI_HAS_EXPIRATION iff != CDR_ZERO_TIME_NANOS, as in the SQL form.
+ *   non_retriable_errors: the activity row's list<text> rule, the body 0B + value written into
+ *     gen_bytes and interned from there.
+ *   completion_event, its encoding, cancel_request_id, event_store_version: parsed over, dropped.
+ *   branch_token: null or empty is no token and no CDR_XI_HAS_BRANCH (gocql cannot tell them
+ *     apart; the SQL form makes an empty field 104 CDR_LOAD_E_ENCODING); else as field 104.
+ *   auto_reset_points + encoding: a null or empty blob is nil reset points; else as 115 / 116.
+ *   search_attributes, memo (map<text, blob>): a value of 1..3 bytes or an element that runs
+ *     past the value is CDR_DEC_TRUNCATED, a negative count, a null element or another negative
+ *     length CDR_DEC_BAD_SIZE — found in the walk, in field order, as the list's are; bytes
+ *     after the last pair are ignored; a count over CDR_LOAD_MAX_SEARCH_ATTR is CDR_LOAD_E_SHAPE
+ *     (search_attributes first).  CDR_XI_HAS_SEARCH_ATTR / _HAS_MEMO iff the map holds at least
+ *     one pair: Cassandra stores an empty map as null, so unlike the SQL form (where the flag is
+ *     the field's presence) an empty map's flag does not come back.  Search-attribute rows as
+ *     in the SQL loader (repeated keys merged).  The Memo handle is the thrift struct body 0D 00
+ *     0A 0B 0B + the CQL map body (count and pairs: a [bytes] element and a thrift binary are
+ *     both a big-endian int32 length and the bytes, so the pairs are copied) + 00, written into
+ *     gen_bytes, hashed while written and interned from there.
+ *   replication_state body, null or empty: not 2DC.  Else CDR_BUILDER_2DC, repl.present = 1 and
+ *     the fields in declaration order (schema.cql:91-97): current_version, start_version (both
+ *     also persist's), last_write_version, last_write_event_id, last_replication_info — a map
+ *     of text -> replication_info{version, last_event_id} with the maps' wire rules (a null
+ *     value is a UDT without fields), its keys matched against the clusters' names: an unknown
+ *     key is CDR_LOAD_E_CLUSTER, a repeated key keeps the last.
+ *   version_histories body, non-empty: CDR_BUILDER_NDC; the encoding column must be "thriftrw",
+ *     the blob's rules are fields 122 / 124's.  With a non-empty replication_state too:
+ *     CDR_LOAD_E_SHAPE (:1270).
+ * exec_status[w] is the first finding in this order: the execution UDT's, in field order; the
+ * replication state's wire findings; both set (SHAPE); an unknown cluster; the branch token; the
+ * reset points; the maps' counts; the version histories — inside the nested blobs level by
+ * level as in cdr_load_state.
+ * gen_bytes: the child rows' run IDs (36 * n_rows[2] bytes), then each entry's share — its UUID
+ * texts (up to five), the list body and the Memo body, rounded up to 4 bytes — then the
+ * activity rows' list bodies.  CDR_API_EINVAL as cdr_load_cql_rows, and for a null column of
+ * `exec` with n_entries != 0 and n_clusters > CDR_MAX_CLUSTERS. */
+typedef struct cdr_cql_exec_in { /* device pointers, offsets into cdr_cql_rows_in.bytes */
+  const uint64_t* execution_off;         /* [n_entries + 1]  body of the `execution` UDT value */
+  const uint64_t* replication_state_off; /* [n_entries + 1]  body of `replication_state` (empty: null) */
+  const uint64_t* version_histories_off; /* [n_entries + 1]  the blob (empty: null) */
+  const uint64_t* vh_encoding_off;       /* [n_entries + 1]  version_histories_encoding text */
+  uint32_t cluster_seed[CDR_MAX_CLUSTERS];
+  uint32_t n_clusters, _pad;
+} cdr_cql_exec_in;
+typedef struct cdr_cql_state_out { /* device buffers owned by the context */
+  cdr_cql_rows_out rows;
+  cdr_exec_persist* persist; /* [n_entries] */
+  uint32_t* builder;         /* [n_entries] */
+  int32_t* exec_status;      /* [n_entries] */
+} cdr_cql_state_out;
+int cdr_load_cql_state(cdr_ctx* ctx, const cdr_cql_rows_in* rows, const cdr_cql_exec_in* exec,
+                       cdr_cql_state_out* out, void* stream);
+
+/* Device milliseconds of the last cdr_load_rows / cdr_load_state / cdr_load_cql_rows /
+ * cdr_load_cql_state on the context (the Cassandra forms' map split counts into ms[0]), between HIP events on its
  * stream: ms[0] the count pass (with the row -> entry map), ms[1] the intern pass and the
  * string ranking (with the two host round trips that size the table and the sort), ms[2] the
  * row ranking, ms[3] the fill pass and the entry epilogue.  The call is synchronous and holds

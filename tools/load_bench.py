@@ -29,6 +29,15 @@ the same states' SQL rows in the same process — the yardstick — with the rat
 and per pass.  The map split counts into the first pass.
 
     python tools/load_bench.py --form cql --out profiles/load_cql.json
+
+--form cql --exec-rows measures whole stored states from Cassandra (cdr_load_cql_state): the
+same four populations with their execution rows (the `execution` / `replication_state` /
+`version_histories` columns behind the tables', column-major; in the distinct run every
+workflow has a run ID of its own), beside cdr_load_state on the same states' SQL rows — the
+yardstick — and cdr_load_cql_rows alone on the same columns, so the execution rows' added
+time is a difference within one process and session.
+
+    python tools/load_bench.py --form cql --exec-rows --out profiles/load_cql_state.json
 """
 import argparse
 import ctypes as C
@@ -221,25 +230,68 @@ def tile_cols(cols: rows.CqlCols, tile: int, timer_suffix: bool = False) -> rows
     return rows.CqlCols(np.concatenate(segs), offs, n * tile)
 
 
-def time_load_cql(eng, cols: rows.CqlCols, reps: int) -> dict:
-    """cdr_load_cql_rows over `cols` (seeds: "" alone), wall clock and passes."""
+def with_exec_cols(T: rows.CqlCols, cols: rows.CqlCols, tile: int, distinct: bool) -> rows.CqlCols:
+    """T (tiled) with the execution row's four columns of `cols` (one population, untiled)
+    `tile` times over behind its bytes, column-major.  distinct: every entry's run ID (the
+    UDT's third field) is its own."""
+    import struct
+    segs, offs, pos = [T.bytes], [], len(T.bytes)
+    n = cols.n_entries
+    for c in range(4):
+        o = cols.exec.off[c]
+        seg = np.tile(cols.bytes[int(o[0]):int(o[-1])], tile)
+        off = tile_offsets(o, tile, pos, np.uint64)
+        if c == 0 and distinct:
+            at = np.zeros(n, np.int64)  # the run ID's place in each base entry's body
+            for w in range(n):
+                body = cols.exec_column(0, w)
+                p = 4 + max(0, struct.unpack_from(">i", body, 0)[0])
+                p += 4 + max(0, struct.unpack_from(">i", body, p)[0])
+                assert struct.unpack_from(">i", body, p)[0] == 16
+                at[w] = p + 4
+            where = (off[:-1].astype(np.int64) - pos) + np.tile(at, tile)
+            ids = np.arange(n * tile, dtype=">u4").view(np.uint8).reshape(-1, 4)
+            seg[where[:, None] + np.arange(4)[None, :]] = ids
+        offs.append(off)
+        segs.append(seg)
+        pos += len(seg)
+    return rows.CqlCols(np.concatenate(segs), T.col_off, T.n_entries, exec=rows.CqlExec(offs, cols.exec.cluster_seed))
+
+
+def time_load_cql(eng, cols: rows.CqlCols, reps: int, exec_rows: bool = False) -> dict:
+    """cdr_load_cql_rows over `cols` — cdr_load_cql_state with exec_rows, where cols.exec holds
+    the execution row's columns and, as cluster_seed, the clusters' names — (seeds: "" and those
+    names), wall clock and passes."""
     L = abi.lib()
     n_bytes = int(len(cols.bytes))
     dev = rows.DeviceBuffers()
     try:
-        sb, so = ingest.string_table([b""])
+        seeds = [b""] + (list(cols.exec.cluster_seed) if exec_rows else [])
+        sb, so = ingest.string_table(seeds)
         inp = abi.CdrCqlRowsIn()
         inp.bytes, inp.n_bytes = dev.up(cols.bytes), n_bytes
         for t in range(5):
             inp.col_off[t] = dev.up(cols.col_off[t])
         inp.seed_bytes, inp.seed_off = dev.up(sb), dev.up(so)
-        inp.n_entries, inp.n_seeds = cols.n_entries, 1
+        inp.n_entries, inp.n_seeds = cols.n_entries, len(seeds)
         wall, passes = [], [[] for _ in PASSES]
         res = abi.CdrCqlRowsOut()
+        if exec_rows:
+            sout, xin = abi.CdrCqlStateOut(), abi.CdrCqlExecIn()
+            X = cols.exec
+            xin.execution_off, xin.replication_state_off = dev.up(X.off[0]), dev.up(X.off[1])
+            xin.version_histories_off, xin.vh_encoding_off = dev.up(X.off[2]), dev.up(X.off[3])
+            xin.n_clusters = len(seeds) - 1
+            for i in range(xin.n_clusters):
+                xin.cluster_seed[i] = 1 + i
         for rep in range(reps + 1):
             assert dev.hip.hipDeviceSynchronize() == 0
             t0 = time.perf_counter()
-            rc = L.cdr_load_cql_rows(eng.ctx, C.byref(inp), C.byref(res), None)
+            if exec_rows:
+                rc = L.cdr_load_cql_state(eng.ctx, C.byref(inp), C.byref(xin), C.byref(sout), None)
+                res = sout.rows
+            else:
+                rc = L.cdr_load_cql_rows(eng.ctx, C.byref(inp), C.byref(res), None)
             t1 = time.perf_counter()
             assert rc == 0 and res.rows.n_bad_entries == 0, (rc, res.rows.n_bad_entries)
             ms = (C.c_float * 4)()
@@ -257,6 +309,9 @@ def time_load_cql(eng, cols: rows.CqlCols, reps: int) -> dict:
     for name, xs in zip(PASSES, passes):
         s = stats(xs)
         rec["passes"][name] = {"s": s, "rows_per_s": sum(n_rows) / s["median"]}
+    if exec_rows:
+        rec["exec_rows"] = cols.n_entries
+        rec["exec_bytes"] = int(cols.exec.off[3][-1] - cols.exec.off[0][0])
     return rec
 
 
@@ -279,6 +334,41 @@ def bench_config_cql(eng, cfg: int, base: int, tile: int, reps: int) -> dict:
         cql = time_load_cql(eng, cql_cols, reps)
         assert sum(cql["rows"].values()) == sum(sql_rows.n_rows) and cql["strings"] == sql["strings"]
         rec["populations"][name] = {"load_rows": sql, "load_cql_rows": cql, "cql_over_sql": versus(cql, sql)}
+    return rec
+
+
+def cql_state_strings(b, out, extra: int) -> list:
+    """rows.whole_state_strings with the create request IDs as UUID texts: the Cassandra writer
+    binds them to a uuid column."""
+    strs = rows.whole_state_strings(b, out, extra=extra)
+    for w in range(b.n_wfs):
+        h = out.exec[w].create_request_id
+        if out.result[w].code == abi.OK and h and len(strs[h]) != 36:
+            strs[h] = b"c0de%04x-0000-4000-8000-%012x" % (h & 0xFFFF, h)
+    assert len(set(strs)) == len(strs)
+    return strs
+
+
+def bench_config_cql_state(eng, cfg: int, base: int, tile: int, reps: int) -> dict:
+    b = engine.synth_batch(cfg, base, seed=0x5EED0000 + cfg)
+    out = eng.replay(b)
+    n_cl = b.cluster.n_clusters
+    xs = cql_state_strings(b, out, n_cl)
+    names = list(range(len(xs) - n_cl, len(xs)))
+    X = rows.encode_state(eng, b, out, xs, exec_rows=True, cluster_names=names)
+    X.exec.cluster_seed = xs[len(xs) - n_cl:]
+    R = tile_rows(X, tile)
+    cols = rows.encode_state_cql(eng, b, out, xs, exec_rows=True, cluster_names=names)
+    cols.exec.cluster_seed = xs[len(xs) - n_cl:]
+    rec = {"config": cfg, "workflows": R.n_entries, "base_workflows": base, "tile": tile, "populations": {}}
+    for name, distinct in (("shared", False), ("distinct_timer_ids", True)):
+        sql = time_load(eng, with_exec_rows(distinct_timer_ids(R) if distinct else R, X, tile, distinct), reps)
+        T = with_exec_cols(tile_cols(cols, tile, distinct), cols, tile, distinct)
+        tables = time_load_cql(eng, T, reps)
+        state = time_load_cql(eng, T, reps, exec_rows=True)
+        assert sum(state["rows"].values()) == sum(R.n_rows)
+        rec["populations"][name] = {"load_state": sql, "load_cql_rows": tables, "load_cql_state": state,
+                                    "cql_over_sql": versus(state, sql), "added": added(state, tables)}
     return rec
 
 
@@ -356,6 +446,7 @@ def main():
     ap.add_argument("--ingest-bytes", type=int, default=2_000_000_000)
     ap.add_argument("--out", default="")
     ap.add_argument("--form", default="sql", choices=("sql", "cql"))
+    ap.add_argument("--exec-rows", action="store_true", help="--form cql: whole states (cdr_load_cql_state)")
     args = ap.parse_args()
     try:
         import torch
@@ -367,9 +458,11 @@ def main():
            "build_flags": int(abi.lib().cdr_build_flags()), "reps": args.reps,
            "timing": "wall clock around the synchronous calls on a warm context (first call dropped); passes: HIP "
                      "events inside cdr_load_rows / cdr_load_state (the intern interval holds its two host round trips)",
-           "seeds": 1, "form": args.form, "configs": []}
+           "seeds": 1, "form": args.form + ("+exec-rows" if args.exec_rows else ""), "configs": []}
     for cfg in (int(c) for c in args.configs.split(",")):
-        if args.form == "cql":
+        if args.form == "cql" and args.exec_rows:
+            r = bench_config_cql_state(eng, cfg, args.base, args.tile, args.reps)
+        elif args.form == "cql":
             r = bench_config_cql(eng, cfg, args.base, args.tile, args.reps)
         else:
             r = bench_config(eng, cfg, args.base, args.tile, args.reps, args.ingest_bytes)
