@@ -298,6 +298,39 @@ SYNC_GROUPS = (4, 8, 16, 64)
 AI_HEARTBEAT_TIME_SET = 0x8
 E_VH_EMPTY, P_UNKNOWN_WF_STATE = 25, 36
 TT_ACTIVITY_TIMEOUT = 17
+# standby task verification on loaded states (schema.h cdr_standby_task / cdr_standby_result)
+CdrStandbyTask = _S("cdr_standby_task", [("task", CdrTask), ("wf", i32), ("flags", u32), ("tag", i64)])
+CdrStandbyResult = _S("cdr_standby_result", [
+    ("action", i32), ("reason", i32), ("code", i32), ("flags", u32), ("next_event_id", i64),
+    ("last_write_version", i64), ("act_row", u32), ("task_row", u32), ("push_timeout_s", i32), ("task_list", u32),
+    ("tag", i64), ("_pad", u64), ("timer_task", CdrTask)])
+SBT_GLOBAL_DOMAIN, SBT_LAST_ATTEMPT = 0x1, 0x2
+SB_ACTIONS = {0: "DONE", 1: "RETRY", 2: "FETCH", 3: "DISCARDED", 4: "PUSH_ACTIVITY", 5: "PUSH_DECISION",
+              6: "RECORD_STARTED", 7: "UPSERT", 8: "RECORD_CLOSED", 9: "UPDATED", 10: "HOST", 11: "E_STATE",
+              12: "E_TASK_TYPE"}
+(SB_DONE, SB_RETRY, SB_FETCH, SB_DISCARDED, SB_PUSH_ACTIVITY, SB_PUSH_DECISION, SB_RECORD_STARTED, SB_UPSERT,
+ SB_RECORD_CLOSED, SB_UPDATED, SB_HOST, SB_E_STATE, SB_E_TASK_TYPE) = range(13)
+SB_REASONS = (
+    "NO_WORKFLOW", "STALE_EVENT_ID", "NOT_RUNNING", "USER_TIMER_NONE", "USER_TIMER_PENDING", "ACT_TIMER_PENDING",
+    "ACT_TIMER_NO_UPDATE", "ACT_TIMER_UPDATED", "DECISION_S2S", "DECISION_GONE", "DECISION_VERSION",
+    "DECISION_PENDING", "BACKOFF_DECIDED", "BACKOFF_PENDING", "WF_TIMEOUT_VERSION", "WF_TIMEOUT_PENDING",
+    "RETRY_TIMER", "DELETE_HISTORY", "UNKNOWN_TIMER", "XACT_GONE", "XACT_VERSION", "XACT_STARTED", "XACT_PENDING",
+    "XDEC_GONE", "XDEC_VERSION", "XDEC_STARTED", "XDEC_PENDING", "CLOSE_RUNNING", "CLOSE_VERSION", "CLOSE_RECORD",
+    "CANCEL_GONE", "CANCEL_VERSION", "CANCEL_PENDING", "SIGNAL_GONE", "SIGNAL_VERSION", "SIGNAL_PENDING",
+    "CHILD_GONE", "CHILD_VERSION", "CHILD_STARTED", "CHILD_PENDING", "STARTED_VERSION", "STARTED_RECORD",
+    "UPSERT_RECORD", "RESET_WORKFLOW", "UNKNOWN_TRANSFER", "BAD_STATE", "E_LAST_WRITE_VERSION", "E_START_VERSION",
+    "E_WF_STATE")  # cdr_sb_reason, in order: SBR_<name> = index
+for _i, _n in enumerate(SB_REASONS):
+    globals()["SBR_" + _n] = _i
+SB_STATE_UPDATED, SB_HAS_TIMER_TASK = 0x1, 0x2
+SB_NO_ROW = 0xFFFFFFFF
+MAX_TASK_TIMEOUT = 31622400  # CDR_MAX_TASK_TIMEOUT
+STANDBY_GROUP = 4  # CDR_STANDBY_GROUP (cdr.h)
+STANDBY_GROUPS = (4, 8, 16, 64)
+(TT_DECISION, TT_ACTIVITY, TT_CLOSE_EXECUTION, TT_CANCEL_EXECUTION, TT_START_CHILD, TT_SIGNAL_EXECUTION,
+ TT_RECORD_STARTED, TT_RESET_WORKFLOW, TT_UPSERT_SA) = range(9)
+(TT_DECISION_TIMEOUT, TT_ACTIVITY_TIMEOUT, TT_USER_TIMER, TT_WORKFLOW_TIMEOUT, TT_DELETE_HISTORY, TT_ACTIVITY_RETRY_TIMER,
+ TT_WORKFLOW_BACKOFF) = range(16, 23)
 CdrSlices = _S("cdr_slices", [
     ("n_slices", u32), ("_pad", u32), ("n_rows", u64), ("arena_words", u64)] + [(n, C.c_void_p) for n in (
         "slice_row0", "slice_len", "lane_wf", "slab", "arena", "slice_scratch_off", "slice_act_slots",
@@ -400,6 +433,7 @@ MIRRORS = {
     "cdr_opts": CdrOpts, "cdr_ingest_in": CdrIngestIn, "cdr_ingest_out": CdrIngestOut,
     "cdr_mut_info": CdrMutInfo, "cdr_mutation": CdrMutation,
     "cdr_sync_activity": CdrSyncActivity, "cdr_sync_result": CdrSyncResult,
+    "cdr_standby_task": CdrStandbyTask, "cdr_standby_result": CdrStandbyResult,
     "cdr_rows_in": CdrRowsIn, "cdr_rows_out": CdrRowsOut,
     "cdr_exec_rows_in": CdrExecRowsIn, "cdr_state_out": CdrStateOut,
     "cdr_cql_rows_in": CdrCqlRowsIn, "cdr_cql_rows_out": CdrCqlRowsOut,
@@ -456,6 +490,13 @@ EXPORTS = {
                                       C.POINTER(CdrTotals), C.POINTER(CdrOut), C.POINTER(CdrClusterMeta), C.c_void_p,
                                       C.c_void_p]),
     "cdr_set_sync_group": (i32, [C.c_void_p, i32]),
+    "cdr_plan_standby": (i32, [C.c_void_p, u32, u32, C.c_void_p, C.c_void_p]),
+    "cdr_standby_tasks_async": (i32, [C.c_void_p, C.c_void_p, C.c_void_p, u32, u32, C.c_void_p, C.POINTER(CdrOut),
+                                      C.POINTER(CdrClusterMeta), i64, i64, C.c_void_p, C.c_void_p]),
+    "cdr_standby_tasks_batch": (i32, [C.c_void_p, C.c_void_p, C.c_void_p, u32, u32, C.c_void_p,
+                                      C.POINTER(CdrTotals), C.POINTER(CdrOut), C.POINTER(CdrClusterMeta), i64, i64,
+                                      C.c_void_p, C.c_void_p]),
+    "cdr_set_standby_group": (i32, [C.c_void_p, i32]),
     "cdr_plan_class_ranges": (i32, [C.c_void_p, u32, C.c_void_p, C.c_void_p]),
     "cdr_compact_async": (i32, [C.c_void_p, i32, C.POINTER(CdrDevBatch), C.POINTER(CdrOut), C.c_void_p,
                                 C.c_void_p, C.c_void_p]),

@@ -52,6 +52,8 @@ enum cdr_ws_slot {
   WS_MUT_DEL_TIMER, WS_MUT_DEL_CHILD, WS_MUT_DEL_CANCEL, WS_MUT_DEL_SIGNAL, WS_MUT_INFO,
   // cdr_sync_activity_batch (sync.hip): requests, their CSR and results (the states reuse WS_CY_*)
   WS_SYNC_REQ, WS_SYNC_OFF, WS_SYNC_RES,
+  // cdr_standby_tasks_batch (standby.hip): the same three of its own (the states reuse WS_CY_*)
+  WS_SB_REQ, WS_SB_OFF, WS_SB_RES,
   // cdr_load_rows (load.hip): outputs and scratch of their own, so that a later
   // cdr_ingest_decode leaves a loaded state valid
   WS_LD_ROWENT, WS_LD_STATUS, WS_LD_DEST, WS_LD_TKEY, WS_LD_FAIL, WS_LD_ESTATUS, WS_LD_RESULT, WS_LD_CAPS,
@@ -95,6 +97,7 @@ struct cdr_ctx {
   int cls = CDR_CLS_ON;                // cdr_set_cls_path (CDR_CLS_*)
   uint32_t plan_mode = CDR_PLAN_WAVE | CDR_PLAN_PAR;  // cdr_set_plan_mode
   int sync_group = CDR_SYNC_GROUP;     // cdr_set_sync_group
+  int standby_group = CDR_STANDBY_GROUP;  // cdr_set_standby_group
   hipEvent_t ev[4];
   bool timed;
   // optional per-launch timing ring (bench): event pairs around every replay kernel

@@ -1154,12 +1154,15 @@ int32_t cdr_workflow_id_to_shard(const char* workflow_id, size_t len, int32_t nu
   return (int32_t)(cdr_fingerprint32(workflow_id, len) % (uint32_t)num_shards);
 }
 
-// stable counting sort of the requests by state; strangers (wf < 0 or past the states) last
-int cdr_plan_sync(const cdr_sync_activity* reqs, uint32_t n_req, uint32_t n_states, uint32_t* order,
-                  uint32_t* req_off) {
+// stable counting sort of request records by state; strangers (wf < 0 or past the states) last.
+// The record's int32 `wf` is read at byte offset wf_at of a record of `stride` bytes, so the
+// sync and the standby planner share it.
+static int plan_by_state(const void* reqs, size_t stride, size_t wf_at, uint32_t n_req, uint32_t n_states,
+                         uint32_t* order, uint32_t* req_off) {
   if (!req_off || (n_req && (!reqs || !order))) return CDR_API_EINVAL;
   auto group = [&](uint32_t i) -> uint32_t {
-    const int32_t wf = reqs[i].wf;
+    int32_t wf;
+    std::memcpy(&wf, (const char*)reqs + (size_t)i * stride + wf_at, sizeof(wf));
     return wf < 0 || (uint32_t)wf >= n_states ? n_states : (uint32_t)wf;
   };
   const uint64_t n_groups = (uint64_t)n_states + 1;
@@ -1169,6 +1172,18 @@ int cdr_plan_sync(const cdr_sync_activity* reqs, uint32_t n_req, uint32_t n_stat
   std::vector<uint32_t> pos(req_off, req_off + n_groups);
   for (uint32_t i = 0; i < n_req; i++) order[pos[group(i)]++] = i;
   return CDR_API_OK;
+}
+
+int cdr_plan_sync(const cdr_sync_activity* reqs, uint32_t n_req, uint32_t n_states, uint32_t* order,
+                  uint32_t* req_off) {
+  return plan_by_state(reqs, sizeof(cdr_sync_activity), offsetof(cdr_sync_activity, wf), n_req, n_states, order,
+                       req_off);
+}
+
+int cdr_plan_standby(const cdr_standby_task* reqs, uint32_t n_req, uint32_t n_states, uint32_t* order,
+                     uint32_t* req_off) {
+  return plan_by_state(reqs, sizeof(cdr_standby_task), offsetof(cdr_standby_task, wf), n_req, n_states, order,
+                       req_off);
 }
 
 const char* cdr_version(void) { return "cadence_amd-cdr 0.1 (gfx950)"; }
@@ -1223,6 +1238,8 @@ uint64_t cdr_struct_size(const char* name) {
       {"cdr_mutation", sizeof(cdr_mutation)},
       {"cdr_sync_activity", sizeof(cdr_sync_activity)},
       {"cdr_sync_result", sizeof(cdr_sync_result)},
+      {"cdr_standby_task", sizeof(cdr_standby_task)},
+      {"cdr_standby_result", sizeof(cdr_standby_result)},
       {"cdr_rows_in", sizeof(cdr_rows_in)},
       {"cdr_rows_out", sizeof(cdr_rows_out)},
       {"cdr_exec_rows_in", sizeof(cdr_exec_rows_in)},

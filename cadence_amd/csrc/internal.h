@@ -42,6 +42,20 @@ CDR_HD act_timer act_first_timer(const Row& a) {
   }
   return best;
 }
+// The earliest expiry over all of a row's activity timers, created or not: what the standby
+// timer processor's expiry loop meets first (timerQueueStandbyProcessor.go:308-329 looks at the
+// head of the sorted list only).  It is the first timer's time, whatever its task status.
+template <class Row>
+CDR_HD int64_t act_earliest_expiry(const Row& a) {
+  return act_first_timer(a).t;
+}
+// time.Time.Unix() of a nanosecond instant: whole seconds, floored (also below zero), as
+// IsTimerExpired compares them (timerBuilder.go:198-203)
+CDR_HD int64_t unix_seconds(int64_t ns) {
+  constexpr int64_t kSec = 1000000000LL;
+  const int64_t q = ns / kSec;
+  return (ns % kSec) < 0 ? q - 1 : q;
+}
 // the timer_task_status bit of a timeout type (getActivityTimerStatus, timerBuilder.go:36-47)
 CDR_HD int32_t act_timer_bit(int32_t type) {
   return type == CDR_TIMEOUT_HEARTBEAT          ? CDR_TTS_HEARTBEAT

@@ -810,6 +810,70 @@ class Engine:
             out[int(k)] = res[i]
         return out
 
+    def set_standby_group(self, lanes: int) -> int:
+        """Lanes per state of the standby kernel (4, 8, 16 or 64; cdr_set_standby_group): a
+        measurement knob, every value computes the same bytes.  Returns the previous value."""
+        prev = int(abi.lib().cdr_set_standby_group(self.ctx, int(lanes)))
+        if prev < 0:
+            raise ValueError(f"standby group {lanes}: not one of {abi.STANDBY_GROUPS}")
+        return prev
+
+    def standby_tasks(self, state: Outputs, reqs, now: int, delay: int, via: str = "batch", cluster=None):
+        """The standby processors' verification of `reqs` (a standby.Requests, in arrival order)
+        against the loaded states `state` at clock `now` with StandbyClusterDelay `delay` (both
+        ns): groups the requests by state (cdr_plan_standby), verifies them through
+        cdr_standby_tasks_batch (host buffers, the default) or, with via="async", through
+        cdr_standby_tasks_async on device copies made with the HIP runtime — the same kernel
+        either way — and updates state.tables["act"] in place.  Returns the cdr_standby_result
+        array, element i for reqs[i]."""
+        from . import standby
+        L = abi.lib()
+        n, ns = len(reqs), state.n_wfs
+        cluster = cluster if cluster is not None else default_cluster()
+        order, req_off = standby.plan(reqs, ns)
+        grouped = reqs.gathered(order)
+        res = (abi.CdrStandbyResult * max(1, n))()
+        pl = state.plan
+        if via == "batch":
+            rc = L.cdr_standby_tasks_batch(self.ctx, C.addressof(grouped), req_off.ctypes.data, n, ns,
+                                           C.addressof(pl.caps), C.byref(pl.totals), C.byref(state.cstruct()),
+                                           C.byref(cluster), now, delay, C.addressof(res), None)
+            if rc:
+                raise RuntimeError(f"cdr_standby_tasks_batch rc={rc}")
+        else:
+            hip = _hip()
+            ptrs = []
+
+            def up(x, nb=None):
+                nb = C.sizeof(x) if nb is None else nb
+                p = C.c_void_p()
+                if hip.hipMalloc(C.byref(p), C.c_size_t(max(8, nb))) != 0:
+                    raise RuntimeError("hipMalloc failed")
+                ptrs.append(p)
+                if nb and hip.hipMemcpy(p, x if isinstance(x, int) else C.addressof(x), C.c_size_t(nb), 1) != 0:
+                    raise RuntimeError("hipMemcpy H2D failed")
+                return p.value
+            try:
+                o = abi.CdrOut()
+                o.result, o.exec, o.repl = up(state.result), up(state.exec), up(state.repl)
+                for t in ("vh", "act", "timer", "child", "cancel", "signal"):
+                    setattr(o, t, up(state.tables[t]))
+                d_res = up(res)
+                rc = L.cdr_standby_tasks_async(self.ctx, up(grouped), up(req_off.ctypes.data, req_off.nbytes), n, ns,
+                                               up(pl.caps), C.byref(o), C.byref(cluster), now, delay, d_res, None)
+                if rc:
+                    raise RuntimeError(f"cdr_standby_tasks_async rc={rc}")
+                for host, dev in ((state.tables["act"], o.act), (res, d_res)):  # hipMemcpy synchronises
+                    if hip.hipMemcpy(C.addressof(host), dev, C.c_size_t(C.sizeof(host)), 2) != 0:
+                        raise RuntimeError("hipMemcpy D2H failed")
+            finally:
+                for p in ptrs:
+                    hip.hipFree(p)
+        out = (abi.CdrStandbyResult * max(1, n))()
+        for i, k in enumerate(order):
+            out[int(k)] = res[i]
+        return out
+
     def rebuild(self, batch: Batch, pl: Plan | None = None, advanced_visibility: bool = True, snapshot: bool = False) -> Outputs:
         """nDCStateRebuilder.rebuild's device half through cdr_rebuild_batch: replay
         (every kernel) then refreshTasks (refresh.hip) with now = batch.now_ns; the

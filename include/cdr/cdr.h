@@ -767,6 +767,81 @@ int cdr_sync_activity_batch(cdr_ctx* ctx, const cdr_sync_activity* reqs, const u
 #define CDR_SYNC_GROUP 4
 int cdr_set_sync_group(cdr_ctx* ctx, int lanes);
 
+/* ---------------------------------------------- standby task verification (standby.hip) */
+/* Batched timerQueueStandbyProcessorImpl.process / transferQueueStandbyProcessorImpl.process
+ * (service/history/timerQueueStandbyProcessor.go:173-225, transferQueueStandbyProcessor.go:
+ * 137-204) on loaded states in cdr_out form: the standby cluster's consumer of the tasks
+ * cdr_out.transfer / timer_tasks hold.  schema.h cdr_standby_task / cdr_standby_result describe
+ * the records, cdr_sb_action what the caller does, cdr_sb_reason the exit taken.  Per request:
+ *
+ *   load (loadMutableStateForTimerTask / ...TransferTask, xdcUtil.go:95-169): wf < 0 is DONE;
+ *     event_id >= next_event_id is DONE (there is one copy of the state: the reload finds the
+ *     same) unless the task is a DecisionTimeout / DecisionTask with decision_schedule_id ==
+ *     event_id and decision_attempt > 0; then the IsWorkflowExecutionRunning gate of processTimer
+ *     (timerQueueStandbyProcessor.go:555-558) / processTransfer (transferQueueStandbyProcessor.go:
+ *     580-583; CloseExecution passes it, processTaskIfClosed).  The type switch comes first: the
+ *     types it answers without a state (ActivityRetryTimer, DeleteHistoryEvent, ResetWorkflow,
+ *     a ScheduleToStart DecisionTimeout, an unknown type) read no state, but a failed record or
+ *     wf >= n_states is E_STATE for every type.
+ *   shouldProcessTask is the caller's domain filter: it submits only tasks it would process.
+ *   verifyTaskVersion (xdcUtil.go:71-91): passes without CDR_SBT_GLOBAL_DOMAIN, else compares
+ *     the entity's version with task.version.
+ *   discardTask (timerQueueStandbyProcessor.go:618-626, transferQueueStandbyProcessor.go:652-660):
+ *     now - visibility_ts > 3 * standby_delay (the difference saturates as time.Sub does); a
+ *     pending entity gives RETRY without it, FETCH with it, DISCARDED with it on the last attempt.
+ *   UserTimer (:227-276): the earliest expiry_time over the state's timer rows against
+ *     visibility_ts, both floored to whole seconds (IsTimerExpired, timerBuilder.go:198-203;
+ *     time.Unix() floors, also below zero).  The reference looks at the head of the sorted list
+ *     only and flooring is monotonic, so this is a min-reduction.
+ *   ActivityTimeout (:278-374): the same over the earliest timer of every activity row
+ *     (loadActivityTimers, timerBuilder.go:249-312); when none has expired, a Heartbeat task
+ *     clears CDR_TTS_HEARTBEAT on its row if the row exists (:341-348), GetActivityTimerTaskIfNeeded
+ *     runs as in cdr_sync_activity_async (same tie rule), and if either changed something the
+ *     result is UPDATED with the rows, the task and last_write_version (:359-372).
+ *   DecisionTimeout (:376-427), WorkflowBackoffTimer (:429-473; HasProcessedOrPendingDecision,
+ *     mutableStateDecisionTaskManager.go:731-733), WorkflowTimeout (:475-513; GetStartVersion,
+ *     mutableStateBuilder.go:504-524: repl.start_version for 2DC, the first version-history item's
+ *     version for NDC, CDR_EMPTY_VERSION for a local builder).
+ *   ActivityTask (transferQueueStandbyProcessor.go:206-246), DecisionTask (:248-295; the timeout
+ *     is min(workflow_timeout, CDR_MAX_TASK_TIMEOUT)): pushToMatching = now - visibility_ts >
+ *     standby_delay.  CloseExecution (:297-361), CancelExecution (:363-400), SignalExecution
+ *     (:402-439), StartChildExecution (:441-482), RecordWorkflowStarted / UpsertWorkflowSearch
+ *     Attributes (:484-550).
+ *
+ * Requests of one state apply in order (an UPDATED ActivityTimeout changes what the next
+ * request of the state sees); states are independent.
+ *
+ * cdr_plan_standby (host): cdr_plan_sync's contract for cdr_standby_task (req_off has
+ * n_states + 2 entries; strangers form the trailing group). */
+int cdr_plan_standby(const cdr_standby_task* reqs, uint32_t n_req, uint32_t n_states, uint32_t* order,
+                     uint32_t* req_off);
+/* Verifies the grouped requests: the contract of cdr_sync_activity_async — reqs [n_req], req_off
+ * [at least n_states + 1], state_caps [n_states], the arrays `state` names and res [n_req] are
+ * device memory, `state` and `cluster` host structs; a record whose result.code != CDR_OK is not
+ * touched; rows of one state are in ascending unique key order.  Of `state` result, exec, repl,
+ * vh, act, timer, child, cancel and signal are read.  state->act is updated in place by UPDATED
+ * requests only, and only the timer_task_status of the rows the result names; every other byte
+ * of act keeps its value.  now_ns: shard.GetCurrentTime(clusterName), already delayed;
+ * standby_delay_ns: StandbyClusterDelay.  res[i] belongs to reqs[i].  One launch, no
+ * allocation, no host round trip; asynchronous on `stream`.  CDR_API_EINVAL for null arguments
+ * or standby_delay_ns <= 0. */
+int cdr_standby_tasks_async(cdr_ctx* ctx, const cdr_standby_task* reqs, const uint32_t* req_off, uint32_t n_req,
+                            uint32_t n_states, const cdr_wf_caps* state_caps, const cdr_out* state,
+                            const cdr_cluster_meta* cluster, int64_t now_ns, int64_t standby_delay_ns,
+                            cdr_standby_result* res, void* stream);
+/* The same for host buffers (as cdr_sync_activity_batch): requests, req_off and the states'
+ * records (sized by state_totals) are uploaded into the context's grow-only workspace, the same
+ * kernel runs, then state->act and res are downloaded.  Synchronous on `stream`; one call at a
+ * time per context. */
+int cdr_standby_tasks_batch(cdr_ctx* ctx, const cdr_standby_task* reqs, const uint32_t* req_off, uint32_t n_req,
+                            uint32_t n_states, const cdr_wf_caps* state_caps, const cdr_totals* state_totals,
+                            const cdr_out* state, const cdr_cluster_meta* cluster, int64_t now_ns,
+                            int64_t standby_delay_ns, cdr_standby_result* res, void* stream);
+/* Lanes that work on one state in the standby kernel: 4, 8, 16 or 64, as cdr_set_sync_group.
+ * Returns the previous value, or CDR_API_EINVAL.  Every value computes the same bytes. */
+#define CDR_STANDBY_GROUP 4
+int cdr_set_standby_group(cdr_ctx* ctx, int lanes);
+
 /* Stream compaction of the per-workflow pending tables into dense tables
  * (device pointers): for each table, rows [caps.off, caps.off + result.n) of every
  * workflow are copied to dense[row_base[w] ...]; row_base is an exclusive scan of

@@ -831,6 +831,138 @@ static_assert(sizeof(cdr_sync_activity) == 64, "cdr_sync_activity");
 static_assert(sizeof(cdr_sync_result) == 128 && offsetof(cdr_sync_result, timer_task) == 64, "cdr_sync_result");
 #endif
 
+/* ============================================================ STANDBY TASKS ===
+ * timerQueueStandbyProcessorImpl.process and transferQueueStandbyProcessorImpl.process
+ * (service/history/timerQueueStandbyProcessor.go:173-225, transferQueueStandbyProcessor.go:
+ * 137-204) on loaded states: the standby cluster's verification of the transfer and timer
+ * tasks the replay and refreshTasks emit.  One request is one task as cdr_out.transfer /
+ * timer_tasks hold it, the state it addresses, and what the caller resolved for it. */
+/* verifyTaskVersion's two lookups (xdcUtil.go:71-91) came out "global domains are enabled and
+ * the task's domain is global": the version check compares.  Without the bit it passes.  (A
+ * domain the cache does not know is the caller's error: it does not submit the task.) */
+#define CDR_SBT_GLOBAL_DOMAIN 0x1u
+/* the processors' lastAttempt: the re-verification fetchHistoryAndVerifyOnce runs after the
+ * history fetch (timerQueueStandbyProcessor.go:570-591, transferQueueStandbyProcessor.go:605-626) */
+#define CDR_SBT_LAST_ATTEMPT 0x2u
+typedef struct cdr_standby_task {
+  cdr_task task;  /* type, timeout_type, event_id, visibility_ts, attempt, task_list, version are read */
+  int32_t wf;     /* index of the loaded state (the caller resolves it); < 0: workflow not found */
+  uint32_t flags; /* CDR_SBT_* */
+  int64_t tag;    /* the caller's cookie, copied to the result */
+} cdr_standby_task;
+
+/* what the caller does with the task */
+enum cdr_sb_action {
+  CDR_SB_DONE = 0,      /* the processor returns nil: acknowledge the task */
+  CDR_SB_RETRY = 1,     /* ErrTaskRetry: the replicated event has not arrived */
+  CDR_SB_FETCH = 2,     /* discardTask (timerQueueStandbyProcessor.go:618-626, transferQueueStandbyProcessor.go:
+                           651-660) and not the last attempt: re-replicate from next_event_id
+                           (fetchHistoryFromRemote), then submit again with CDR_SBT_LAST_ATTEMPT */
+  CDR_SB_DISCARDED = 3, /* the same exit on the last attempt: ErrTaskDiscarded (xdcUtil.go:39-67) */
+  CDR_SB_PUSH_ACTIVITY = 4,  /* pushActivity(task, push_timeout_s) transferQueueStandbyProcessor.go:237-245 */
+  CDR_SB_PUSH_DECISION = 5,  /* pushDecision(task, task_list, push_timeout_s) :286-294 */
+  CDR_SB_RECORD_STARTED = 6, /* recordWorkflowStarted :543-546 (the record's fields are the caller's) */
+  CDR_SB_UPSERT = 7,         /* upsertWorkflowExecution :547-548 */
+  CDR_SB_RECORD_CLOSED = 8,  /* recordWorkflowClosed :347-359 */
+  CDR_SB_UPDATED = 9,   /* processActivityTimeout changed the state, timerQueueStandbyProcessor.go:331-372 */
+  CDR_SB_HOST = 10,     /* TaskTypeDeleteHistoryEvent :218-220: persistence work, passed through */
+  CDR_SB_E_STATE = 11,  /* the addressed record's result.code != CDR_OK or wf >= n_states (nothing read,
+                           nothing written), or a failure of the walk named by `code` and `reason` */
+  CDR_SB_E_TASK_TYPE = 12 /* errUnknownTimerTask :222-223 / errUnknownTransferTask :201-202 */
+};
+/* the exit taken: one value per `return` site.  T: timerQueueStandbyProcessor.go, X:
+ * transferQueueStandbyProcessor.go, U: xdcUtil.go.  "pending" exits give RETRY, or FETCH /
+ * DISCARDED when discardTask holds; the two push exits give RETRY or PUSH_*. */
+enum cdr_sb_reason {
+  CDR_SBR_NO_WORKFLOW = 0,         /* U:98-100, 137-139 EntityNotExists (wf < 0): DONE */
+  CDR_SBR_STALE_EVENT_ID = 1,      /* U:122-127, 161-166 event_id >= next_event_id: DONE */
+  CDR_SBR_NOT_RUNNING = 2,         /* T:555-558, X:580-583: DONE */
+  CDR_SBR_USER_TIMER_NONE = 3,     /* T:273-274 no user timer expired: DONE */
+  CDR_SBR_USER_TIMER_PENDING = 4,  /* T:253-267 */
+  CDR_SBR_ACT_TIMER_PENDING = 5,   /* T:316-323 */
+  CDR_SBR_ACT_TIMER_NO_UPDATE = 6, /* T:355-357: DONE */
+  CDR_SBR_ACT_TIMER_UPDATED = 7,   /* T:359-372: UPDATED */
+  CDR_SBR_DECISION_S2S = 8,        /* T:384-386 ScheduleToStart decision timeout: DONE */
+  CDR_SBR_DECISION_GONE = 9,       /* T:399-403: DONE */
+  CDR_SBR_DECISION_VERSION = 10,   /* T:405-410: DONE */
+  CDR_SBR_DECISION_PENDING = 11,   /* T:419-425 */
+  CDR_SBR_BACKOFF_DECIDED = 12,    /* T:446-450 HasProcessedOrPendingDecision: DONE */
+  CDR_SBR_BACKOFF_PENDING = 13,    /* T:465-471 */
+  CDR_SBR_WF_TIMEOUT_VERSION = 14, /* T:498-503: DONE */
+  CDR_SBR_WF_TIMEOUT_PENDING = 15, /* T:505-511 */
+  CDR_SBR_RETRY_TIMER = 16,        /* T:208-210 ActivityRetryTimer: DONE */
+  CDR_SBR_DELETE_HISTORY = 17,     /* T:218-220: HOST */
+  CDR_SBR_UNKNOWN_TIMER = 18,      /* T:222-223: E_TASK_TYPE */
+  CDR_SBR_XACT_GONE = 19,          /* X:213-217: DONE */
+  CDR_SBR_XACT_VERSION = 20,       /* X:218-223: DONE */
+  CDR_SBR_XACT_STARTED = 21,       /* X:236: DONE */
+  CDR_SBR_XACT_PENDING = 22,       /* X:227-233: RETRY or PUSH_ACTIVITY */
+  CDR_SBR_XDEC_GONE = 23,          /* X:257-260: DONE */
+  CDR_SBR_XDEC_VERSION = 24,       /* X:266-271: DONE */
+  CDR_SBR_XDEC_STARTED = 25,       /* X:285: DONE */
+  CDR_SBR_XDEC_PENDING = 26,       /* X:275-283: RETRY or PUSH_DECISION */
+  CDR_SBR_CLOSE_RUNNING = 27,      /* X:309-312 the workflow is running (reset): DONE */
+  CDR_SBR_CLOSE_VERSION = 28,      /* X:338-343: DONE */
+  CDR_SBR_CLOSE_RECORD = 29,       /* X:347-359: RECORD_CLOSED */
+  CDR_SBR_CANCEL_GONE = 30,        /* X:380-384: DONE */
+  CDR_SBR_CANCEL_VERSION = 31,     /* X:385-390: DONE */
+  CDR_SBR_CANCEL_PENDING = 32,     /* X:392-398 */
+  CDR_SBR_SIGNAL_GONE = 33,        /* X:419-423: DONE */
+  CDR_SBR_SIGNAL_VERSION = 34,     /* X:424-429: DONE */
+  CDR_SBR_SIGNAL_PENDING = 35,     /* X:431-437 */
+  CDR_SBR_CHILD_GONE = 36,         /* X:458-462: DONE */
+  CDR_SBR_CHILD_VERSION = 37,      /* X:463-468: DONE */
+  CDR_SBR_CHILD_STARTED = 38,      /* X:470-472: DONE */
+  CDR_SBR_CHILD_PENDING = 39,      /* X:474-480 */
+  CDR_SBR_STARTED_VERSION = 40,    /* X:514-524: DONE */
+  CDR_SBR_STARTED_RECORD = 41,     /* X:543-546: RECORD_STARTED */
+  CDR_SBR_UPSERT_RECORD = 42,      /* X:547-548: UPSERT */
+  CDR_SBR_RESET_WORKFLOW = 43,     /* X:191-193: DONE */
+  CDR_SBR_UNKNOWN_TRANSFER = 44,   /* X:201-202: E_TASK_TYPE */
+  CDR_SBR_BAD_STATE = 45,          /* result.code != CDR_OK or wf >= n_states: E_STATE, code CDR_OK */
+  CDR_SBR_E_LAST_WRITE_VERSION = 46, /* GetLastWriteVersion failed, T:337-340, X:334-337: E_STATE, CDR_E_VH_EMPTY */
+  CDR_SBR_E_START_VERSION = 47,    /* GetStartVersion failed, T:494-497, X:515-518: E_STATE, CDR_E_VH_EMPTY */
+  CDR_SBR_E_WF_STATE = 48,         /* IsWorkflowExecutionRunning panics: E_STATE, CDR_P_UNKNOWN_WF_STATE */
+  CDR_SBR_COUNT = 49
+};
+#define CDR_SB_STATE_UPDATED 0x1u  /* UPDATED: the heartbeat task's row went through UpdateActivity (act_row; T:342-347,
+                                      whether or not its bit was set) */
+#define CDR_SB_HAS_TIMER_TASK 0x2u /* UPDATED: GetActivityTimerTaskIfNeeded created timer_task */
+#define CDR_SB_NO_ROW 0xFFFFFFFFu
+#define CDR_MAX_TASK_TIMEOUT 31622400 /* common.MaxTaskTimeout (common/constants.go:77), seconds */
+
+/* Per request.  Fields that do not apply are zero (rows: CDR_SB_NO_ROW).  The builder kind of
+ * a state is read as for cdr_sync_result.  `code` is CDR_OK except for the walk's failures
+ * (reasons E_*), after which nothing is written to the state. */
+typedef struct cdr_standby_result {
+  int32_t action; /* cdr_sb_action */
+  int32_t reason; /* cdr_sb_reason */
+  int32_t code;   /* cdr_status */
+  uint32_t flags; /* CDR_SB_* (UPDATED only) */
+  int64_t next_event_id;      /* the state's: fetchHistoryFromRemote's argument (FETCH), the Condition of
+                                 the passive update (UPDATED); set by every exit that has loaded the state
+                                 (STALE_EVENT_ID and later), 0 for NO_WORKFLOW, BAD_STATE and the types
+                                 answered without a state */
+  int64_t last_write_version; /* with next_event_id: what UpdateCurrentVersion(lastWriteVersion, true)
+                                 takes (T:363); CDR_EMPTY_VERSION where GetLastWriteVersion fails */
+  /* UPDATED: absolute row indices into state->act of the rows to upsert — act_row the row whose
+   * heartbeat bit was cleared, task_row the row whose timer_task_status gained a bit */
+  uint32_t act_row, task_row;
+  int32_t push_timeout_s; /* PUSH_*: min(ScheduleToStartTimeout | WorkflowTimeout, CDR_MAX_TASK_TIMEOUT) */
+  uint32_t task_list;     /* PUSH_*: the task's task_list handle */
+  int64_t tag;
+  uint64_t _pad;
+  /* CDR_SB_HAS_TIMER_TASK: as cdr_sync_result.timer_task.  (For a Heartbeat timer_task the reference also
+   * sets ActivityInfo.LastHeartbeatTimeoutVisibility, timerBuilder.go:223-225: a field the records do
+   * not hold; the caller sets it from timer_task.visibility_ts.) */
+  cdr_task timer_task;
+} cdr_standby_result;
+#ifdef __cplusplus
+static_assert(sizeof(cdr_standby_task) == 80 && sizeof(cdr_standby_task) % 16 == 0, "cdr_standby_task");
+static_assert(sizeof(cdr_standby_result) == 128 && offsetof(cdr_standby_result, timer_task) == 64,
+              "cdr_standby_result");
+#endif
+
 /* ==================================================== NDC VERSION HISTORIES ===
  * The persisted VersionHistories of an NDC workflow (common/persistence/versionHistory.go:
  * VersionHistories{currentVersionHistoryIndex, histories []*VersionHistory}), one branch
