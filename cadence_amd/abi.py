@@ -53,7 +53,8 @@ STATUS = {
     13: "E_BAD_INPUT", 14: "E_REFRESH_EVENT_NOT_FOUND", 15: "E_REFRESH_BACKOFF_INITIATOR",
     16: "E_REFRESH_CAPACITY", 17: "E_VH_NO_LCA", 18: "E_VH_LCA_NOT_CONTAINED", 19: "E_VH_FIRST_ITEM_MISMATCH",
     20: "E_NDC_RETRY_TASK", 21: "E_NDC_BRANCH_CHANGED", 22: "E_NDC_SAME_VERSION", 23: "E_REBUILD_VH_MISMATCH",
-    24: "E_VHS_CAPACITY", 25: "E_VH_EMPTY", 32: "P_ACTIVITY_STARTED_NIL", 33: "P_CHILD_STARTED_NIL",
+    24: "E_VHS_CAPACITY", 25: "E_VH_EMPTY", 26: "E_XDC_MORE_THAN_2DC", 27: "E_XDC_MISSING_REPL_INFO",
+    28: "E_XDC_REMOTE_HIGHER_VERSION", 29: "E_XDC_CORRUPTED_REPL_INFO", 32: "P_ACTIVITY_STARTED_NIL", 33: "P_CHILD_STARTED_NIL",
     34: "P_VH_ITEM_INVALID", 35: "P_UNKNOWN_CLUSTER", 36: "P_UNKNOWN_WF_STATE", 64: "NOT_APPLIED", 65: "NOT_RUN",
     66: "E_LOAD_ROWS",
 }
@@ -402,6 +403,40 @@ CdrNdcRound = _S("cdr_ndc_round", [("tasks", C.c_void_p), ("task_items", C.c_voi
                                    ("rebuild_out", CdrOut), ("apply", CdrDevBatch), ("apply_out", CdrOut),
                                    ("dec", C.c_void_p), ("refresh_now", i64), ("refresh_flags", u32), ("_pad", u32)])
 
+# 2DC replication tasks (schema.h cdr_xdc_task / cdr_xdc_decision, cdr.h cdr_xdc_round)
+CdrXdcTask = _S("cdr_xdc_task", [
+    ("version", i64), ("first_event_id", i64), ("next_event_id", i64), ("last_event_version", i64),
+    ("last_event_task_id", i64), ("n_events", u32), ("first_event_type", u32), ("flags", u32), ("ri_mask", u32),
+    ("cur_state", i32), ("cur_close_status", i32), ("cur_last_write_version", i64), ("cur_last_event_task_id", i64),
+    ("cur_next_event_id", i64), ("_pad", u64), ("ri_version", i64 * MAX_CLUSTERS),
+    ("ri_last_event_id", i64 * MAX_CLUSTERS)])
+CdrXdcDecision = _S("cdr_xdc_decision", [
+    ("code", i32), ("action", i32), ("reason", i32), ("via", i32), ("reset_event_id", i64),
+    ("hint_next_event_id", i64), ("hint_run", u32), ("reapply_to", u32), ("terminate_current_first", u32),
+    ("flags", u32), ("cas_prev_is_self", u32), ("cas_prev_state", i32), ("cas_prev_last_write_version", i64)])
+CdrXdcRound = _S("cdr_xdc_round", [("tasks", C.c_void_p), ("reset", CdrDevBatch), ("reset_out", CdrOut),
+                                   ("apply", CdrDevBatch), ("apply_out", CdrOut), ("dec", C.c_void_p)])
+(XDC_RESET_WORKFLOW, XDC_NO_STATE, XDC_HAS_BUFFERED, XDC_CUR_PRESENT, XDC_CUR_IS_SELF,
+ XDC_CUR_RUNNING) = (1 << b for b in range(6))
+XDC_ACTIONS = ("DROP", "APPLY", "APPLY_FRESH", "RESET_APPLY", "REAPPLY", "RETRY", "FLUSH_BUFFER",
+               "APPLY_RESET_EVENT")  # cdr_xdc_action, in order: XDC_<name> = index
+for _i, _n in enumerate(XDC_ACTIONS):
+    globals()["XDC_" + _n] = _i
+XDC_REASONS = (
+    "EMPTY_TASK", "DUPLICATE_START", "START", "MISSING_NO_CURRENT", "MISSING_STALE", "MISSING_NEWER_RESET",
+    "MISSING_NEWER", "MISSING_SAME_OLDER_TASK", "MISSING_SAME_RUNNING", "MISSING_SAME_RESET", "MISSING_SAME_CLOSED",
+    "STALE_RUNNING", "STALE_SELF", "STALE_OTHER", "RESET_ABANDONED", "FLUSH_BUFFER", "RESET_REJECTED",
+    "RESET_CONFLICT", "DUPLICATE", "CLOSED_AHEAD", "BUFFER", "CLOSED", "APPLY", "E_STATE", "E_NO_CURRENT",
+    "E_WF_STATE", "E_CLUSTER", "E_MORE_THAN_2DC", "E_MISSING_REPL_INFO", "E_REMOTE_HIGHER_VERSION",
+    "E_CORRUPTED_REPL_INFO", "E_RESET_PREFIX", "E_RESET_REPLAY")  # cdr_xdc_reason, in order: XDR_<name> = index
+for _i, _n in enumerate(XDC_REASONS):
+    globals()["XDR_" + _n] = _i
+XDR_ROUND_ONLY = ("E_RESET_PREFIX", "E_RESET_REPLAY")  # exits of cdr_xdc_replicate_async's reset step
+XDV_NONE, XDV_SAME_VERSION, XDV_SAME_CLUSTER, XDV_EVENT_ID_MATCH, XDV_RESET = range(5)
+XDD_RESET_RAN, XDD_CAS_VERSION_FROM_TERMINATE = 0x1, 0x2
+E_BAD_INPUT, P_UNKNOWN_CLUSTER, NOT_RUN = 13, 35, 65
+E_XDC_MORE_THAN_2DC, E_XDC_MISSING_REPL_INFO, E_XDC_REMOTE_HIGHER_VERSION, E_XDC_CORRUPTED_REPL_INFO = 26, 27, 28, 29
+
 # ------------------------------------------------------------------ synth
 CdrSynthParams = _S("cdr_synth_params", [
     ("config", i32), ("n_wfs", u32), ("seed", u64), ("target_len", u32), ("max_len", u32), ("error_rate", f64),
@@ -431,6 +466,7 @@ MIRRORS = {
     "cdr_task": CdrTask, "cdr_vh_token": CdrVHToken, "cdr_vh_branch": CdrVHBranch, "cdr_vhs": CdrVHS,
     "cdr_ndc_task": CdrNdcTask, "cdr_ndc_decision": CdrNdcDecision, "cdr_ndc_round": CdrNdcRound, "cdr_last_decision": CdrLastDecision,
     "cdr_opts": CdrOpts, "cdr_ingest_in": CdrIngestIn, "cdr_ingest_out": CdrIngestOut,
+    "cdr_xdc_task": CdrXdcTask, "cdr_xdc_decision": CdrXdcDecision, "cdr_xdc_round": CdrXdcRound,
     "cdr_mut_info": CdrMutInfo, "cdr_mutation": CdrMutation,
     "cdr_sync_activity": CdrSyncActivity, "cdr_sync_result": CdrSyncResult,
     "cdr_standby_task": CdrStandbyTask, "cdr_standby_result": CdrStandbyResult,
@@ -511,6 +547,12 @@ EXPORTS = {
                                  C.c_void_p]),
     "cdr_ndc_replicate_async": (i32, [C.c_void_p, u32, C.POINTER(CdrNdcRound), C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.POINTER(CdrOut), C.c_void_p]),
+    "cdr_xdc_admit_host": (i32, [C.c_void_p, u32, C.c_void_p, C.POINTER(CdrOut), C.POINTER(CdrClusterMeta),
+                                 C.c_void_p]),
+    "cdr_xdc_admit_async": (i32, [C.c_void_p, C.c_void_p, u32, C.c_void_p, C.POINTER(CdrOut),
+                                  C.POINTER(CdrClusterMeta), C.c_void_p, C.c_void_p]),
+    "cdr_xdc_replicate_async": (i32, [C.c_void_p, u32, C.POINTER(CdrXdcRound), C.c_void_p, C.POINTER(CdrOut),
+                                      C.POINTER(CdrClusterMeta), C.c_void_p]),
     "cdr_plan_ndc_apply": (i32, [C.POINTER(CdrBatch), C.c_void_p, C.c_void_p, C.POINTER(CdrTotals)]),
     "cdr_fingerprint32": (u32, [C.c_char_p, C.c_size_t]),
     "cdr_workflow_id_to_shard": (i32, [C.c_char_p, C.c_size_t, i32]),

@@ -44,6 +44,8 @@ enum cdr_ws_slot {
   WS_ENC_SIZES, WS_ENC_TMP,
   // cdr_ndc_replicate_async (ndc.hip)
   WS_NDC_SKIP_RB, WS_NDC_SKIP_AP, WS_NDC_INMEM, WS_NDC_SRC, WS_NDC_CARRY,
+  // cdr_xdc_replicate_async (xdc.hip)
+  WS_XDC_SKIP_RS, WS_XDC_SKIP_AP, WS_XDC_SRC, WS_XDC_CARRY,
   WS_RETRY,  // the class kernels' retry lists: 8 counters, then a list of n_slices per class
   WS_TSTAGE, WS_THEAD,  // k_replay_cls<TASKS>: staged task records, per-entry headers (k_tasks_merge)
   WS_CLS_MAP,  // the device class sort's per-event (class, position), type word and annotation (k_cls_count -> k_cls_gather)

@@ -21,6 +21,7 @@
 #include "cdr/ingest.h"
 #include "internal.h"
 #include "pack_event.h"
+#include "xdc_admit.h"
 
 namespace {
 
@@ -1186,6 +1187,20 @@ int cdr_plan_standby(const cdr_standby_task* reqs, uint32_t n_req, uint32_t n_st
                        req_off);
 }
 
+// the 2DC admission decision (xdc_admit.h) over host records: what k_xdc_admit computes
+int cdr_xdc_admit_host(const cdr_xdc_task* tasks, uint32_t n, const cdr_wf_caps* state_caps, const cdr_out* state,
+                       const cdr_cluster_meta* cluster, cdr_xdc_decision* dec) {
+  (void)state_caps;  // the decision reads no table rows
+  if (!cluster || cluster->failover_version_increment <= 0 || cluster->n_clusters <= 0 ||
+      cluster->n_clusters > CDR_MAX_CLUSTERS || cluster->current_cluster < 0 ||
+      cluster->current_cluster >= cluster->n_clusters)
+    return CDR_API_EINVAL;
+  if (n && (!tasks || !dec || !state || !state->result || !state->exec || !state->repl)) return CDR_API_EINVAL;
+  for (uint32_t w = 0; w < n; w++)
+    dec[w] = cdr_xdc::admit(tasks[w], state->result[w], state->exec[w], state->repl[w], *cluster);
+  return CDR_API_OK;
+}
+
 const char* cdr_version(void) { return "cadence_amd-cdr 0.1 (gfx950)"; }
 
 }  // extern "C"
@@ -1234,6 +1249,9 @@ uint64_t cdr_struct_size(const char* name) {
       {"cdr_ndc_task", sizeof(cdr_ndc_task)},
       {"cdr_ndc_decision", sizeof(cdr_ndc_decision)},
       {"cdr_ndc_round", sizeof(cdr_ndc_round)},
+      {"cdr_xdc_task", sizeof(cdr_xdc_task)},
+      {"cdr_xdc_decision", sizeof(cdr_xdc_decision)},
+      {"cdr_xdc_round", sizeof(cdr_xdc_round)},
       {"cdr_mut_info", sizeof(cdr_mut_info)},
       {"cdr_mutation", sizeof(cdr_mutation)},
       {"cdr_sync_activity", sizeof(cdr_sync_activity)},

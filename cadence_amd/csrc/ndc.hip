@@ -19,6 +19,7 @@
 
 #include "cdr/cdr.h"
 #include "ctx.h"
+#include "round.h"
 
 #define HIPCHK(x)                                                                                     \
   do {                                                                                                \
@@ -32,6 +33,9 @@
 extern "C" int cdr_ctx_device(const cdr_ctx* ctx);  // replay.hip
 
 namespace {
+
+using cdr_round::copy_state;
+using cdr_round::zero_result;
 
 struct It {
   int64_t e, v;
@@ -248,8 +252,6 @@ __global__ __launch_bounds__(256) void k_ndc_rebuild_verify(uint32_t n, const cd
   s.current = d.branch_index;  // SetCurrentVersionHistoryIndex (:172-174)
 }
 
-__device__ void zero_result(cdr_wf_result& r, int32_t code);
-
 __global__ __launch_bounds__(256) void k_vhs_sync(uint32_t n, cdr_vhs* vhs, cdr_vh_item* pool,
                                                   const cdr_wf_caps* caps, cdr_out O) {
   const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
@@ -279,37 +281,6 @@ __global__ __launch_bounds__(256) void k_vhs_sync(uint32_t n, cdr_vhs* vhs, cdr_
 }
 
 // ---- cdr_ndc_replicate_async's steps (one thread per workflow)
-
-__device__ void zero_result(cdr_wf_result& r, int32_t code) {
-  r = cdr_wf_result{};
-  r.code = code;
-}
-
-// the state records of entry w := the source's (rows at the destination's capacities)
-__device__ void copy_state(const cdr_out& S, const cdr_wf_caps& sc, const cdr_out& D, const cdr_wf_caps& dc, uint32_t w) {
-  const cdr_wf_result r = S.result[w];
-  D.exec[w] = S.exec[w];
-  D.repl[w] = S.repl[w];
-  D.result[w] = r;
-  if (r.code != CDR_OK) return;
-  bool ok = true;
-  auto cp = [&](auto* src, auto* dst, uint64_t so, uint64_t doff, uint32_t n, uint32_t cap) {
-    if (n > cap) {
-      ok = false;
-      return;
-    }
-    for (uint32_t i = 0; i < n; i++) dst[doff + i] = src[so + i];
-  };
-  cp(S.act, D.act, sc.act_off, dc.act_off, r.n_activity, dc.act_cap);
-  cp(S.timer, D.timer, sc.timer_off, dc.timer_off, r.n_timer, dc.timer_cap);
-  cp(S.child, D.child, sc.child_off, dc.child_off, r.n_child, dc.child_cap);
-  cp(S.cancel, D.cancel, sc.cancel_off, dc.cancel_off, r.n_cancel, dc.cancel_cap);
-  cp(S.signal, D.signal, sc.signal_off, dc.signal_off, r.n_signal, dc.signal_cap);
-  cp(S.vh, D.vh, sc.vh_off, dc.vh_off, r.n_vh, dc.vh_cap);
-  cp(S.rp, D.rp, sc.rp_off, dc.rp_off, r.n_reset_points, dc.rp_cap);
-  cp(S.sa, D.sa, sc.sa_off, dc.sa_off, r.n_search_attr, dc.sa_cap);
-  if (!ok) D.result[w].code = CDR_E_BAD_INPUT;
-}
 
 // which workflows the rebuild replays (CDR_NDC_REBUILD of a live state); every output
 // record a step will not write is marked CDR_NOT_RUN; the apply carry's src map
@@ -355,8 +326,6 @@ __global__ __launch_bounds__(256) void k_ndc_round_adopt_rebuilt(uint32_t n, con
     skip_ap[w] = 0;
   }
 }
-
-__global__ void k_ndc_carry_desc(cdr_carry* dst, cdr_carry c) { *dst = c; }
 
 // after the apply (+ VH sync): the applied state is the workflow's
 __global__ __launch_bounds__(256) void k_ndc_round_adopt_applied(uint32_t n, const uint8_t* skip_ap,
@@ -422,7 +391,7 @@ int cdr_ndc_replicate_async(cdr_ctx* ctx, uint32_t n, const cdr_ndc_round* R, cd
   cy.state.n_tasks = nullptr;
   cy.state.last_decision = nullptr;
   cy.in_memory = in_mem;
-  hipLaunchKernelGGL(k_ndc_carry_desc, dim3(1), dim3(1), 0, st, carry_d, cy);
+  hipLaunchKernelGGL(cdr_round::k_carry_desc, dim3(1), dim3(1), 0, st, carry_d, cy);
   HIPCHK(hipGetLastError());
   cdr_dev_batch ap = R->apply;
   ap.skip = skip_ap;

@@ -935,6 +935,72 @@ int cdr_ndc_replicate_async(cdr_ctx* ctx, uint32_t n, const cdr_ndc_round* round
  * loaded state has at most state_caps[w] rows; every entry replays in the general kernel). */
 int cdr_plan_ndc_apply(const cdr_batch* b, const cdr_wf_caps* state_caps, cdr_wf_caps* caps, cdr_totals* totals);
 
+/* ------------------------------------------- 2DC replication rounds (xdc.hip) */
+/* historyReplicator.ApplyEvents (service/history/historyReplicator.go:339-763, H below) for one
+ * task per workflow: the replication path while EnableNDC is off.
+ *
+ *   cdr_xdc_admit_host / cdr_xdc_admit_async: task[w] against the target run's records
+ *     (state->result / exec / repl [w]; not read for a task with CDR_XDC_NO_STATE) -> dec[w]:
+ *     the empty-task and start-event exits (H:377-410), ApplyOtherEventsMissingMutableState
+ *     (H:451-519), ApplyOtherEventsVersionChecking (H:521-653) with
+ *     conflictResolutionTerminateCurrentRunningIfNotSelf (H:925-999) and getLatestCheckpoint
+ *     (H:1115-1140), then, for a state that passes, ApplyOtherEvents' event-id check (H:664-686)
+ *     and ApplyReplicationTask's running check (H:704-707).  One function (csrc/xdc_admit.h)
+ *     compiled for both; the host form takes host records, the device form device records and
+ *     runs on `stream`.  The state is not written.  Valid alone, for callers that stage their
+ *     own replays: a task whose events end in ContinuedAsNew goes this way.  tasks / dec are
+ *     16-byte aligned; state_caps is not read (the decision reads no table rows).
+ *   What the decision only names is the caller's — everything on the active side that writes
+ *     events: reapplyEvents (REAPPLY), terminateWorkflow (terminate_current_first),
+ *     flushEventsBuffer (FLUSH_BUFFER), resetor.ApplyResetEvent (APPLY_RESET_EVENT), and
+ *     replicateWorkflowStarted's create-workflow handling after an APPLY_FRESH. */
+int cdr_xdc_admit_host(const cdr_xdc_task* tasks, uint32_t n, const cdr_wf_caps* state_caps, const cdr_out* state,
+                       const cdr_cluster_meta* cluster, cdr_xdc_decision* dec);
+int cdr_xdc_admit_async(cdr_ctx* ctx, const cdr_xdc_task* tasks, uint32_t n, const cdr_wf_caps* state_caps,
+                        const cdr_out* state, const cdr_cluster_meta* cluster, cdr_xdc_decision* dec, void* stream);
+
+/* One round of 2DC replication tasks over n workflows, device-resident end to end, for task
+ * w of workflow w:
+ *   1. admit (k_xdc_admit, as cdr_xdc_admit_async) -> dec[w]; every record of reset_out /
+ *      apply_out a later step will not write gets result.code CDR_NOT_RUN;
+ *   2. CDR_XDC_RESET_APPLY: conflictResolverImpl.reset (conflictResolver.go:66-184) — entry w of
+ *      `reset` (the workflow's events 1 .. reset_event_id, 2DC builder; its applyEvents calls
+ *      are the pages the caller read, :94-133, the last one trimmed to the reset point)
+ *      replayed on a fresh builder, the other entries masked.  A replay that does not end at
+ *      next_event_id == reset_event_id + 1 fails the workflow with CDR_E_BAD_INPUT (the wrong
+ *      prefix).  The loaded state's BranchToken replaces the Started event's (:141-142;
+ *      StartTimestamp, :144-146, is not in the records).  With reset_out.transfer /
+ *      timer_tasks / n_tasks set, the replay emits the stateBuilder's task lists, which the
+ *      snapshot persists (stateBuilder.go:606-608, conflictResolver.go:150-162; the extra
+ *      UpsertWorkflowSearchAttributesTask of :159-162 is the caller's): `reset` is then
+ *      planned without wave slices and, where it carries class-sorted blocks, with task_rows.
+ *      The reset state replaces state[w] (the reference has persisted it, :166-183) and
+ *      dec[w] gains CDR_XDD_RESET_RAN;
+ *   3. ApplyOtherEvents (H:655-694) against the reset state — dec[w] can turn from RESET_APPLY
+ *      into DROP or RETRY — then ApplyReplicationTask (H:696-763) of every workflow still to
+ *      apply: entry w of `apply` replayed onto state[w] as a loaded state (in_memory = 0: the
+ *      reference re-loads after a reset, conflictResolver.go:183), APPLY_FRESH entries on a
+ *      fresh builder (ApplyStartEvent H:436-449);
+ *   4. state[w] := the applied state.  A failed replay leaves its error in state->result[w]
+ *      (a failed reset also in dec[w], reasons CDR_XDR_E_RESET_*).  DROP, REAPPLY, RETRY,
+ *      FLUSH_BUFFER and APPLY_RESET_EVENT leave the state as it was, or as the reset left it.
+ *      A decision error (dec[w].code) leaves the state untouched: the reference returns the
+ *      error without writing.
+ * `reset` / `apply` are device-resident batches with entry w = workflow w and no continue-as-new
+ * entries; `apply` is planned with cdr_plan_ndc_apply(state_caps), without fast or wave slices
+ * (else CDR_API_EINVAL).  The apply's own task lists are not emitted.  No device allocation
+ * once the context's workspace is warm, no host round trip; asynchronous on `stream`. */
+typedef struct cdr_xdc_round {
+  const cdr_xdc_task* tasks; /* [n] device */
+  cdr_dev_batch reset;       /* entry w: events 1 .. reset point of workflow w */
+  cdr_out reset_out;
+  cdr_dev_batch apply;       /* entry w: the task's events */
+  cdr_out apply_out;
+  cdr_xdc_decision* dec;     /* [n] device, out */
+} cdr_xdc_round;
+int cdr_xdc_replicate_async(cdr_ctx* ctx, uint32_t n, const cdr_xdc_round* round, const cdr_wf_caps* state_caps,
+                            const cdr_out* state, const cdr_cluster_meta* cluster, void* stream);
+
 /* ------------------------------------------- loading persisted rows (load.hip) */
 /* The inverse of the row encoders above for the SQL form: the five pending tables' row
  * blobs decoded on the device, straight into the loaded-state tables cdr_carry takes — what

@@ -181,6 +181,11 @@ enum cdr_status {
   CDR_E_REBUILD_VH_MISMATCH = 23,   /* rebuilt VH != branch VH nDCConflictResolver.go:154-165 */
   CDR_E_VHS_CAPACITY = 24,          /* branch / item slots exhausted (caller-planned) */
   CDR_E_VH_EMPTY = 25,              /* GetFirstItem / GetLastItem on an empty history :399-420 */
+  /* 2DC historyReplicator.ApplyOtherEventsVersionChecking (historyReplicator.go) */
+  CDR_E_XDC_MORE_THAN_2DC = 26,     /* ErrMoreThan2DC :595 */
+  CDR_E_XDC_MISSING_REPL_INFO = 27, /* ErrImpossibleLocalRemoteMissingReplicationInfo :608-612 */
+  CDR_E_XDC_REMOTE_HIGHER_VERSION = 28, /* ErrImpossibleRemoteClaimSeenHigherVersion :620-624 */
+  CDR_E_XDC_CORRUPTED_REPL_INFO = 29, /* ErrCorruptedReplicationInfo :628-633 */
   CDR_P_ACTIVITY_STARTED_NIL = 32,  /* nil deref mutableStateBuilder.go:2089-2091 */
   CDR_P_CHILD_STARTED_NIL = 33,     /* nil deref mutableStateBuilder.go:3319-3320 */
   CDR_P_VH_ITEM_INVALID = 34,       /* NewVersionHistoryItem panic versionHistory.go:36-42 */
@@ -1018,6 +1023,121 @@ typedef struct cdr_ndc_decision {
   cdr_vh_item lca;                /* FindLCAVersionHistoryIndexAndItem's item */
   cdr_vh_token rebuild_token;     /* REBUILD: the branch's token (SetCurrentBranchToken target) */
 } cdr_ndc_decision;
+
+/* ================================================= 2DC REPLICATION TASKS ===
+ * historyReplicator.ApplyEvents (service/history/historyReplicator.go:339-763; H below), the
+ * replication path while EnableNDC is off: what to do with one incoming task — drop, buffer
+ * (retry), apply, or reset the state to the last common checkpoint and then apply.  One
+ * cdr_xdc_task per workflow: the request as ApplyEvents sees it plus the facts it fetches
+ * from outside the target state. */
+#define CDR_XDC_RESET_WORKFLOW 0x01u /* request.ResetWorkflow */
+#define CDR_XDC_NO_STATE 0x02u       /* loading the target run gave EntityNotExists (H:406-410, 415-425) */
+#define CDR_XDC_HAS_BUFFERED 0x04u   /* msBuilder.HasBufferedEvents (the records omit BufferedEvents) */
+#define CDR_XDC_CUR_PRESENT 0x08u    /* the workflow ID has a current run (cur_* are valid) */
+#define CDR_XDC_CUR_IS_SELF 0x10u    /* ... and it is the target run */
+#define CDR_XDC_CUR_RUNNING 0x20u    /* ... and its IsWorkflowExecutionRunning (H:480) */
+typedef struct cdr_xdc_task {
+  int64_t version;                  /* request.Version */
+  int64_t first_event_id, next_event_id;
+  int64_t last_event_version, last_event_task_id; /* of request.History's last event */
+  uint32_t n_events;                /* len(request.History.Events) */
+  uint32_t first_event_type;        /* cdr_event_type of its first event */
+  uint32_t flags;                   /* CDR_XDC_* */
+  uint32_t ri_mask;                 /* request.ReplicationInfo by cluster index, as cdr_repl_state keys its map */
+  /* the current run (getCurrentWorkflowMutableState H:464-480 / GetCurrentExecution H:953-964) */
+  int32_t cur_state, cur_close_status;
+  int64_t cur_last_write_version, cur_last_event_task_id, cur_next_event_id;
+  uint64_t _pad;
+  int64_t ri_version[CDR_MAX_CLUSTERS];
+  int64_t ri_last_event_id[CDR_MAX_CLUSTERS];
+} cdr_xdc_task;
+
+enum cdr_xdc_action {
+  CDR_XDC_DROP = 0,        /* returns nil, the state untouched */
+  CDR_XDC_APPLY = 1,       /* ApplyReplicationTask onto the loaded state */
+  CDR_XDC_APPLY_FRESH = 2, /* ApplyStartEvent: a fresh 2DC builder (H:410, 436-449) */
+  CDR_XDC_RESET_APPLY = 3, /* conflictResolver.reset to reset_event_id, then ApplyOtherEvents on the reset state */
+  CDR_XDC_REAPPLY = 4,     /* stale task: the caller's reapplyEvents on run `reapply_to` */
+  CDR_XDC_RETRY = 5,       /* RetryTaskError with (hint_run, hint_next_event_id) */
+  CDR_XDC_FLUSH_BUFFER = 6, /* the caller runs flushEventsBuffer (H:1211-1242), then resubmits without
+                               CDR_XDC_HAS_BUFFERED */
+  CDR_XDC_APPLY_RESET_EVENT = 7, /* the caller's resetor.ApplyResetEvent */
+  CDR_XDC_ACTION_COUNT = 8
+};
+/* The exit taken, one value per reference exit (H: historyReplicator.go).  An error exit has
+ * action DROP and the error in `code`. */
+enum cdr_xdc_reason {
+  CDR_XDR_EMPTY_TASK = 0,          /* H:377-381 no events: DROP */
+  CDR_XDR_DUPLICATE_START = 1,     /* H:399-405 Started onto an existing run: DROP */
+  CDR_XDR_START = 2,               /* H:410 -> ApplyStartEvent: APPLY_FRESH */
+  CDR_XDR_MISSING_NO_CURRENT = 3,  /* H:465-469 no current run: RETRY (target run, FirstEventID) */
+  CDR_XDR_MISSING_STALE = 4,       /* H:482-486 current run is on a higher version: REAPPLY to it */
+  CDR_XDR_MISSING_NEWER_RESET = 5, /* H:499-501 (after terminating a running current run, :492-498): APPLY_RESET_EVENT */
+  CDR_XDR_MISSING_NEWER = 6,       /* H:502 likewise: RETRY (target run, FirstEventID) */
+  CDR_XDR_MISSING_SAME_OLDER_TASK = 7, /* H:506-510 same version, running, older task id: DROP */
+  CDR_XDR_MISSING_SAME_RUNNING = 8, /* H:511 RETRY (current run, its next event id) */
+  CDR_XDR_MISSING_SAME_RESET = 9,  /* H:514-517 same version, closed: APPLY_RESET_EVENT */
+  CDR_XDR_MISSING_SAME_CLOSED = 10, /* H:518 RETRY (target run, FirstEventID) */
+  CDR_XDR_STALE_RUNNING = 11,      /* H:541-544 state on a higher version, running: REAPPLY to the target */
+  CDR_XDR_STALE_SELF = 12,         /* H:549-553 closed, and the current run: REAPPLY to the target */
+  CDR_XDR_STALE_OTHER = 13,        /* H:554-562 closed, another run is current: REAPPLY to the current */
+  CDR_XDR_RESET_ABANDONED = 14,    /* H:972-975, 1170-1172 the current run is as new as the task: DROP */
+  CDR_XDR_FLUSH_BUFFER = 15,       /* H:635-638, 1216 running with buffered events: FLUSH_BUFFER */
+  CDR_XDR_RESET_REJECTED = 16,     /* H:603-618 events rejected by remote, reset to getLatestCheckpoint: RESET_APPLY */
+  CDR_XDR_RESET_CONFLICT = 17,     /* H:640-648 event-id conflict, reset to ri.LastEventId: RESET_APPLY */
+  CDR_XDR_DUPLICATE = 18,          /* H:664-671 first_event_id < next event id: DROP */
+  CDR_XDR_CLOSED_AHEAD = 19,       /* H:672-677 a gap, and the workflow is closed: DROP */
+  CDR_XDR_BUFFER = 20,             /* H:679-685 a gap: RETRY (target run, its next event id) */
+  CDR_XDR_CLOSED = 21,             /* H:704-707 the workflow is closed: DROP */
+  CDR_XDR_APPLY = 22,              /* H:688-693 -> ApplyReplicationTask: APPLY */
+  CDR_XDR_E_STATE = 23,            /* the target record has result.code != CDR_OK or no repl.present: CDR_E_BAD_INPUT */
+  CDR_XDR_E_NO_CURRENT = 24,       /* H:953-960 GetCurrentExecution of a closed run found nothing (the task lacks
+                                      CDR_XDC_CUR_PRESENT): CDR_E_BAD_INPUT */
+  CDR_XDR_E_WF_STATE = 25,         /* IsWorkflowExecutionRunning panics (H:541, 674, 704, 938, 1216): CDR_P_UNKNOWN_WF_STATE */
+  CDR_XDR_E_CLUSTER = 26,          /* H:576 ClusterNameForFailoverVersion panics: CDR_P_UNKNOWN_CLUSTER */
+  CDR_XDR_E_MORE_THAN_2DC = 27,    /* H:595 */
+  CDR_XDR_E_MISSING_REPL_INFO = 28, /* H:608-612 */
+  CDR_XDR_E_REMOTE_HIGHER_VERSION = 29, /* H:620-624 */
+  CDR_XDR_E_CORRUPTED_REPL_INFO = 30, /* H:628-633 */
+  CDR_XDR_E_RESET_PREFIX = 31,     /* round only: the reset replay did not end at reset_event_id + 1: CDR_E_BAD_INPUT */
+  CDR_XDR_E_RESET_REPLAY = 32,     /* round only: the reset replay, or adopting its state, failed; `code` = its error */
+  CDR_XDR_COUNT = 33
+};
+/* how ApplyOtherEventsVersionChecking handed the state on to ApplyOtherEvents (`via`) */
+enum cdr_xdc_via {
+  CDR_XDV_NONE = 0,          /* the exit came before */
+  CDR_XDV_SAME_VERSION = 1,  /* H:565-568 */
+  CDR_XDV_SAME_CLUSTER = 2,  /* H:586-593 this cluster was not active before; the versions are one cluster's */
+  CDR_XDV_EVENT_ID_MATCH = 3, /* H:651-652 */
+  CDR_XDV_RESET = 4          /* H:618, 648 the reset state */
+};
+#define CDR_XDD_RESET_RAN 0x1u /* round: the conflict reset ran and its state was adopted (whatever `action` says now) */
+/* cas_prev_last_write_version is the current run's BEFORE terminateWorkflow; the reference passes
+ * on the one terminateWorkflow returns (H:984-998): the caller substitutes it */
+#define CDR_XDD_CAS_VERSION_FROM_TERMINATE 0x2u
+/* getLatestCheckpoint (H:1115-1140) ranges over Go maps, so its ties are random in the reference.
+ * Here: the remote map (the task's ri_*) first, then the local map (the state's lri_*), each in
+ * ascending cluster index; a later entry replaces the pick only on a strictly greater version. */
+typedef struct cdr_xdc_decision {
+  int32_t code;   /* cdr_status */
+  int32_t action; /* cdr_xdc_action */
+  int32_t reason; /* cdr_xdc_reason */
+  int32_t via;    /* cdr_xdc_via */
+  int64_t reset_event_id;     /* RESET_APPLY: resetMutableState's lastEventID */
+  int64_t hint_next_event_id; /* RETRY: newRetryTaskErrorWithHint's next event id */
+  uint32_t hint_run;          /* RETRY: 0 = the target run, 1 = the current run */
+  uint32_t reapply_to;        /* REAPPLY: likewise */
+  uint32_t terminate_current_first; /* the caller's terminateWorkflow(current run, version) comes first (H:492-498, 984-998) */
+  uint32_t flags;             /* CDR_XDD_* */
+  /* RESET_APPLY: (prevRunID is the target's, prevLastWriteVersion, prevState) of conflictResolver.reset */
+  uint32_t cas_prev_is_self;
+  int32_t cas_prev_state;
+  int64_t cas_prev_last_write_version;
+} cdr_xdc_decision;
+#ifdef __cplusplus
+static_assert(sizeof(cdr_xdc_task) == 224 && sizeof(cdr_xdc_task) % 16 == 0, "cdr_xdc_task");
+static_assert(sizeof(cdr_xdc_decision) == 64, "cdr_xdc_decision");
+#endif
 
 #ifdef __cplusplus
 }
