@@ -720,7 +720,10 @@ def build_batch(items):
     entries, w = [], 0
     for k, (c, b) in enumerate(items):
         wf = hb.workflow(workflow_id=f"wf-{k}-{c.name}", run_id=f"run-{k}", request_id=f"req-{k}", builder=b,
-                         failover_version=1, expected_next_event_id=c.expected_next_event_id)
+                         failover_version=1, expected_next_event_id=c.expected_next_event_id,
+                         # (tests/effect_cases.py's cases may name their domain and its retention)
+                         domain_id=getattr(c, "domain_id", "domain-id"),
+                         retention_days=getattr(c, "retention_days", 1))
         wf.calls = c.calls
         nr = None
         if c.new_run is not None:

@@ -295,8 +295,9 @@ def _base(c):
     return c.name.split("+")[0]
 
 
-def _refused(route, c, bld, fast_capable):
-    for names, builders, _ in UNREACHABLE[route]:
+def _refused(route, c, bld, fast_capable, table=None):
+    """`table`: another module's UNREACHABLE in this one's form (tests/test_effect_sites.py)."""
+    for names, builders, _ in (UNREACHABLE if table is None else table)[route]:
         if bld not in builders:
             continue
         if names == "*" or (names == "+timer" and "tail" in c.sites) or \
