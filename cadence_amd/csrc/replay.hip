@@ -2717,9 +2717,9 @@ uint32_t cdr_build_flags(void) {
 #ifdef CDR_PAR_PROF
   f |= 1u;
 #endif
-  if (CDR_PAR_PRIO != 0 || CDR_FDEPTH != 2 || CDR_DEPTH != 1 || CDR_TYPED != 1 || CDR_FAST_DELTA != 1 || CDR_FAST_HINT != 1 ||
+  if (CDR_PAR_PRIO != 0 || CDR_FDEPTH != 1 || CDR_DEPTH != 1 || CDR_TYPED != 1 || CDR_FAST_DELTA != 1 || CDR_FAST_HINT != 1 ||
       CDR_VHBF != 1 || CDR_VHQUICK != 1 || CDR_CLS_DEPTH != 1 || CDR_CLS_PDEPTH != 4 || CDR_CLS_DEPTH_PAR != 4 ||
-      CDR_CLS_PDEPTH_PAR != 16 || CDR_WPE_FAST != 3 || CDR_WPE != 3 || CDR_WPE_CLS != 4 || CDR_WPE_CLS0 != 4 ||
+      CDR_CLS_PDEPTH_PAR != 16 || CDR_WPE_FAST != 4 || CDR_WPE != 3 || CDR_WPE_CLS != 4 || CDR_WPE_CLS0 != 4 ||
       CDR_WPE_CLS2 != 2 || FAST_CK != 8u || CDR_FAST_TBUF != 5 || CDR_WPE_FAST_TBUF != 2 || CDR_FAST_UNI != 1 || CDR_FAST_UNI_SKIP != 1 ||
       CDR_NT_FAST != 2 || CDR_NT_CLS != 0 || CDR_FAST_SADDR != 1 || CDR_FAST_QROW != 1 || CDR_CLS_TBUF != 3 ||
       CDR_MERGE_D2 != 0 || sizeof(CDR_STR(CDR_MERGE_ATTR)) != 1 /* the default is no attribute: "" */)

@@ -11,10 +11,10 @@
 // once because only 2DC needs the rest of a failed call — so it needs fewer registers
 // and runs more waves per SIMD.
 #ifndef CDR_WPE_FAST
-#define CDR_WPE_FAST 3 /* 3 waves per SIMD: FD prefetch slots + state fit 168 VGPRs */
+#define CDR_WPE_FAST 4 /* 4 waves per SIMD: FD prefetch slots + state fit 128 VGPRs (121, no scratch), and sixteen one-wave workgroups' LDS fits the CU (FAST_LDS_BYTES) */
 #endif
 #ifndef CDR_FDEPTH
-#define CDR_FDEPTH 2 /* rows in flight per wave */
+#define CDR_FDEPTH 1 /* rows in flight per wave (2: 138 VGPRs, which costs the fourth wave; forced to four it spills) */
 #endif
 constexpr uint32_t FD = CDR_FDEPTH;
 #ifndef CDR_VHBF
@@ -30,7 +30,7 @@ constexpr uint32_t FD = CDR_FDEPTH;
 #define CDR_TQ_NT 1 /* TASKS: the task records leave with nontemporal stores */
 #endif
 #ifndef CDR_WPE_FAST_TBUF
-#define CDR_WPE_FAST_TBUF 2 /* the buffered TASKS instantiation (166 VGPRs, no spill; at 5 x 64 records its LDS, 19.7 KB, allows 2 waves per SIMD) */
+#define CDR_WPE_FAST_TBUF 2 /* the buffered TASKS instantiation (140 VGPRs, no spill; at 5 x 64 records its LDS, 17.5 KB, allows 9 workgroups per CU: 2 waves per SIMD) */
 #endif
 #ifndef CDR_FAST_SADDR
 #define CDR_FAST_SADDR 1 /* the loop's row offsets from a scalar row index clamped to the slice */
@@ -87,9 +87,19 @@ __device__ __forceinline__ Ev ev_take(const Ev& q) {
 #ifndef FAST_CK
 #define FAST_CK 8u /* reset-point checksums cached in LDS (the rest are looked up in their rows) */
 #endif
+// (the entry's output offsets, run id and reset-point capacity are not among them: only the
+// rare steps that store a VersionHistory item or a reset point need them, and those end in a
+// drain anyway, so they read them from the entry's descriptors there)
 enum : uint32_t {
   ZP_DST_TS = 0, ZP_DSC_TS, ZP_DORIG_TS, ZP_LAST_PROCESSED, ZP_COMPLETION_BATCH,
-  ZP_VH_OFF, ZP_RP_OFF, ZP_RUN_RPCAP, ZP_CK0, FAST_COLD = ZP_CK0 + FAST_CK / 2
+  ZP_CLOSE_VER, /* NDC: CurrentVersion as the closing event froze it */
+  ZP_CK0, FAST_COLD = ZP_CK0 + FAST_CK / 2
+};
+// the activity working slot of the fast kernel: k_replay's planes (replay.hip AP_*) without the
+// two timer candidates, which only k_replay's timer pick over several activities reads back
+enum : uint32_t {
+  FP_SID = 0, FP_TS2C, FP_META, FP_VER, FP_STARTED_ID, FP_STARTED_TIME, FP_CANCEL_ID, FP_ROWS, FP_STC_HB, FP_REQ,
+  FAST_ACT_PLANES
 };
 template <class O>
 __device__ __forceinline__ GAS cdr_vh_item* fast_out_vh(const O& o) { return gp(o.vh); }
@@ -99,7 +109,7 @@ __device__ __forceinline__ GAS cdr_reset_point* fast_out_rp(const O& o) { return
 // stays in flight beside the prefetch loads (the waitcnt pass would otherwise count
 // vmcnt as out of order and wait for zero at every prefetch use)
 #define VM_DRAIN() __builtin_amdgcn_s_waitcnt(0x0F70)
-#define FAST_LDS_BYTES ((CDR_ACT_PLANES + FAST_COLD) * CDR_SLICE_WIDTH * sizeof(uint64_t))
+#define FAST_LDS_BYTES ((FAST_ACT_PLANES + FAST_COLD) * CDR_SLICE_WIDTH * sizeof(uint64_t))
 // TASKS: the wave's task-record pool, three planes of CDR_FAST_TBUF x 64 words
 #define FAST_TQ_WORDS (3u * CDR_FAST_TBUF * CDR_SLICE_WIDTH)
 #define FAST_TBUF_BYTES (FAST_TQ_WORDS * sizeof(uint64_t))
@@ -138,21 +148,16 @@ k_replay_fast(cdr_launch L) {
   const uint32_t len = (uint32_t)D.ev_len;
   const bool isVH = D.builder == CDR_BUILDER_NDC;
   const uint32_t EU = B_.empty_uuid;
-  const uint32_t vh_cap = CP.vh_cap;
   // the single activity working slot: plane p at cdr_lds[p * 64 + lane]; after it, the
   // ExecutionInfo fields the loop only writes (read back once at the end), in LDS
   // rather than VGPRs so that the loop fits 128 registers (4 waves per SIMD)
-  const LdsSlots<CDR_ACT_PLANES> A{lane};
-  const LdsSlots<FAST_COLD> Z{CDR_ACT_PLANES * CDR_SLICE_WIDTH + lane};
-  uint32_t hw_act = 0;  // 0 or 1
+  const LdsSlots<FAST_ACT_PLANES> A{lane};
+  const LdsSlots<FAST_COLD> Z{FAST_ACT_PLANES * CDR_SLICE_WIDTH + lane};
   Z.st(0, ZP_DST_TS, 0);
   Z.st(0, ZP_DSC_TS, 0);
   Z.st(0, ZP_DORIG_TS, 0);
   Z.st(0, ZP_LAST_PROCESSED, CDR_EMPTY_EVENT_ID);
   Z.st(0, ZP_COMPLETION_BATCH, 0);
-  Z.st(0, ZP_VH_OFF, (int64_t)CP.vh_off);
-  Z.st(0, ZP_RP_OFF, (int64_t)CP.rp_off);
-  Z.st(0, ZP_RUN_RPCAP, (int64_t)(D.run_id | ((uint64_t)CP.rp_cap << 32)));
 #pragma unroll
   for (uint32_t i = 0; i < FAST_CK / 2; i++) Z.st(0, ZP_CK0 + i, 0);
   // reset point q's checksum (0 when it has none: never a lookup key) into the cache
@@ -172,18 +177,32 @@ k_replay_fast(cdr_launch L) {
     }
     return x;
   };
-#define vh_l (fast_out_vh(O_) + (uint64_t)Z.ld(0, ZP_VH_OFF))
-#define rp_l (fast_out_rp(O_) + (uint64_t)Z.ld(0, ZP_RP_OFF))
+  // the entry's slices inside the loop (rare steps, each ending in a drain): the offsets from
+  // the entry's descriptor there, through an opaque pointer so that no load is hoisted out
+#define CP_L (late(B_.caps)[w])
+#define vh_l (fast_out_vh(O_) + CP_L.vh_off)
+#define rp_l (fast_out_rp(O_) + CP_L.rp_off)
 
-  uint32_t x_flags = 0, dreq = EU, n_vh = 0, n_rp = 0, n_sa = 0, cks_ok = 0, call_first_k = 0, err_k = 0;
-  int32_t x_dt_timeout_value = 0, x_state = CDR_STATE_CREATED, x_close = CDR_CLOSE_NONE, x_signals = 0, dto = 0;
-  int32_t err = len == 0 ? CDR_E_HISTORY_EMPTY : CDR_OK;
+  uint32_t x_flags = 0, dreq = EU, n_vh = 0, n_rp = 0, cks_ok = 0, call_first_k = 0, err_k = 0;
+  int32_t x_signals = 0, dto = 0;
+  // ExecutionInfo.State | CloseStatus << 8 | the activity slot was ever used << 31 (the sign: one compare)
+  uint32_t xs = (uint32_t)CDR_STATE_CREATED | ((uint32_t)CDR_CLOSE_NONE << 8);
+#define XS_STATE (int32_t)(xs & 0xFFu)
+#define XS_CLOSE (int32_t)((xs >> 8) & 0xFFu)
+#define XS_ACT ((int32_t)xs < 0)
   int64_t x_next_event = CDR_FIRST_EVENT_ID;
   int64_t dv = CDR_EMPTY_VERSION, dsched = CDR_EMPTY_EVENT_ID, dstart = CDR_EMPTY_EVENT_ID, datt = 0;
-  int64_t curv = D.failover_version, vh_last_id = 0, vh_last_ver = 0;
-  int64_t call_first_id = 0, prev_id = 0, prev_ver = 0, err_id = 0;
+  // NDC: the last VersionHistory item is (prev_id, prev_ver) — every accepted event leaves
+  // the item's event id at its own id, and the item's version at its own version (a higher one
+  // opens a new item, a lower one fails the entry) — and CurrentVersion is the version of the
+  // event in hand until the workflow closes (stateBuilder.go:134-154), so none of the three
+  // has a register of its own
+  int64_t call_first_id = 0, prev_id = 0, prev_ver = 0;
   uint32_t ld = 0;  // lastDecision bookkeeping (ld_write)
   const bool want_ld = O_.last_decision != nullptr;
+  // a failure ends the lane (done) and keeps its code and row; the failed event's id is read
+  // back from that row after the loop (the event_id column holds every id, implied or not)
+  int32_t err = len == 0 ? CDR_E_HISTORY_EMPTY : CDR_OK;
   bool done = len == 0;
   // ---- stateBuilder tasks (TASKS): counts, and ExecutionInfo.TaskList once Started set it
   uint32_t n_xt = 0, n_tt = 0, tlist = 0;
@@ -199,7 +218,7 @@ k_replay_fast(cdr_launch L) {
   // drains it: one vmcnt for loads and stores).  A record carries its own destination, so the
   // pool's order is free; one pool for the wave, not a buffer per lane, flushes when the wave's
   // records fill it rather than when its busiest lane does.
-  constexpr uint32_t TQ_BASE = (CDR_ACT_PLANES + FAST_COLD) * CDR_SLICE_WIDTH;
+  constexpr uint32_t TQ_BASE = (FAST_ACT_PLANES + FAST_COLD) * CDR_SLICE_WIDTH;
   constexpr uint32_t TQ_CAP = CDR_FAST_TBUF * CDR_SLICE_WIDTH;
   uint32_t n_pool = 0;  // wave-uniform
   const uint64_t t_xoff = TASKS ? (uint64_t)CP.xfer_off : 0u, t_toff = TASKS ? (uint64_t)CP.ttask_off : 0u;
@@ -311,7 +330,6 @@ k_replay_fast(cdr_launch L) {
   do {                                   \
     const bool f_ = (cond);              \
     err = SEL(f_, (int32_t)(code), err); \
-    err_id = SEL(f_, e.id, err_id);      \
     err_k = SEL(f_, k, err_k);           \
     done |= f_;                          \
   } while (0)
@@ -335,21 +353,18 @@ k_replay_fast(cdr_launch L) {
     Ev e = ev_take(Q[0]);
     if (CDR_FAST_HINT) ev_hint(e);  // (an entry's first event carries no delta bit: its id was loaded)
     const uint32_t tn = tf_take(T[0]);
-    Q[0] = FAST_LOAD_OPS(S, el8(k + FD, len, lane), tn);
-    T[0] = load_tf<CDR_NT_FAST>(S, el8(k + 2 * FD, len, lane));
+    Q[0] = FAST_LOAD_OPS(S, el8(FD, len, lane), tn);
+    T[0] = load_tf<CDR_NT_FAST>(S, el8(2 * FD, len, lane));
     call_first_id = SEL(!done, e.id, call_first_id);
-    prev_id = SEL(done, prev_id, e.id);
+    prev_id = SEL(done, prev_id, e.id);  // (done: an empty history)
     prev_ver = SEL(done, prev_ver, e.ver);
     if (isVH) {  // version prelude of the first event (stateBuilder.go:134-154)
       const int32_t code =
           (e.id < 0 || (e.ver < 0 && e.ver != CDR_EMPTY_VERSION)) ? CDR_P_VH_ITEM_INVALID
-          : (vh_cap == 0)                                            ? CDR_E_BAD_INPUT
+          : (CP.vh_cap == 0)                                         ? CDR_E_BAD_INPUT
                                                                      : CDR_OK;
-      curv = SEL(!done, e.ver, curv);
       PFAIL(!done && code != CDR_OK, code);
       n_vh = done ? 0u : 1u;
-      vh_last_ver = e.ver;
-      vh_last_id = e.id;
     }
     {
       const bool mine = !done;  // mutableStateBuilder.go:1639-1716
@@ -359,7 +374,7 @@ k_replay_fast(cdr_launch L) {
       const bool f1 = mine && (af & CDR_SF_HAS_PARENT_DOMAIN) && (af & CDR_SF_PARENT_DOMAIN_MISSING);
       PFAIL(f1, CDR_E_DOMAIN_NOT_FOUND);  // (Created -> Created is always an accepted transition)
       const bool ok = mine && !f1;
-      uint32_t nrp = 0, nsa = 0, xf = CDR_XI_STARTED | (isVH ? CDR_XI_VH_BRANCH : CDR_XI_HAS_BRANCH);
+      uint32_t nrp = 0, xf = CDR_XI_STARTED | (isVH ? CDR_XI_VH_BRANCH : CDR_XI_HAS_BRANCH);
       // the Started half of ExecutionInfo (bytes 0-127, every field written: absent optional
       // fields as zero) assembled in registers and written by the wave together below
       uint32_t h0[32] = {};
@@ -403,7 +418,7 @@ k_replay_fast(cdr_launch L) {
       {  // two 64-B rounds through the activity slot's planes (free until the first schedule):
          // 4 lanes per 64-B segment, each segment one store instruction
         constexpr uint32_t RS = 65;
-        static_assert(17u * RS * 4u <= CDR_ACT_PLANES * CDR_SLICE_WIDTH * sizeof(uint64_t), "the activity planes");
+        static_assert(17u * RS * 4u <= FAST_ACT_PLANES * CDR_SLICE_WIDTH * sizeof(uint64_t), "the activity planes");
         uint32_t* const L32 = (uint32_t*)cdr_lds;
         const uint64_t em = __builtin_amdgcn_read_exec();
         const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(em >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)em, 0u));
@@ -459,7 +474,7 @@ k_replay_fast(cdr_launch L) {
           f_cap |= cnt > cap;
           // each row at its rank among the input keys (ascending, equal keys in input order):
           // k_tables' order, so that a launch of fast slices alone needs no k_tables pass
-          nsa = cnt < cap ? cnt : cap;
+          const uint32_t nsa = cnt < cap ? cnt : cap;  // (the epilogue counts them again: n_sa)
           for (uint32_t q = 0; q < nsa; q++) {
             const cdr_kv kv = gget(gp(B_.kvs) + (off + q));
             uint32_t rank = 0;
@@ -474,9 +489,7 @@ k_replay_fast(cdr_launch L) {
       }
       PFAIL(f_cap, CDR_E_BAD_INPUT);
       n_rp = SEL(ok, nrp, n_rp);
-      n_sa = SEL(ok, nsa, n_sa);
       x_flags = SEL(ok, xf, x_flags);
-      x_dt_timeout_value = SEL(ok, a->task_timeout_s, x_dt_timeout_value);
       if constexpr (TASKS) {  // scheduleWorkflowTimerTask (stateBuilder.go:706-735) + RecordWorkflowStartedTask (:614-616)
         tlist = ok ? a->task_list : 0u;
         const int64_t backoff = ok ? (int64_t)a->first_decision_backoff_s * NS_PER_S : 0;
@@ -525,53 +538,51 @@ k_replay_fast(cdr_launch L) {
     call_first_id = SEL(bf, e.id, call_first_id);
     call_first_k = SEL(bf, k, call_first_k);
     ld = SEL(bf, 0u, ld);
-    prev_id = SEL(done, prev_id, e.id);
-    prev_ver = SEL(done, prev_ver, e.ver);
-    // version prelude (stateBuilder.go:134-154)
+    // version prelude (stateBuilder.go:134-154), against the last item (prev_id, prev_ver)
     if (isVH) {
-      curv = SEL(!done && (x_state == CDR_STATE_CREATED || x_state == CDR_STATE_RUNNING), e.ver, curv);
 #if CDR_VHQUICK
       // the common step: the packer's delta bits say event_id = the previous event's + 1 and
-      // version = the previous event's, and the previous event left vh_last_id / vh_last_ver
-      // equal to its own id / version (an accepted event always does) — so the item checks
+      // version = the previous event's, and the last item is the previous event's id / version
+      // (prev_id, prev_ver: an accepted event always leaves it so) — so the item checks
       // pass and no item is added; only a non-negative id remains to check.  When every
       // replaying lane is such a step, the full prelude below is skipped.
       const bool quick = done || (n_vh != 0 && (e.tf & CDR_SEF_ID_NEXT) && (e.tf & CDR_SEF_VER_SAME) && e.id >= 0);
-      if (__builtin_amdgcn_ballot_w64(!quick) == 0) {
-        vh_last_id = SEL(done, vh_last_id, e.id);
-      } else
+      if (__builtin_amdgcn_ballot_w64(!quick) != 0)
 #endif
       {
 #if CDR_VHBF
       // the same decision tree as selects over non-short-circuit conditions (no branches)
+      const uint32_t vh_cap = CP_L.vh_cap;
       const bool has = n_vh != 0;
-      const bool newitem = !has | (e.ver > vh_last_ver);
+      const bool newitem = !has | (e.ver > prev_ver);
       const bool b_inv = (e.id < 0) | ((e.ver < 0) & (e.ver != CDR_EMPTY_VERSION));
-      const bool b_ver = has & (e.ver < vh_last_ver);
-      const bool b_id = has & (e.id <= vh_last_id);
+      const bool b_ver = has & (e.ver < prev_ver);
+      const bool b_id = has & (e.id <= prev_id);
       const bool b_cap = newitem & (n_vh >= vh_cap);
       int32_t code = b_cap ? (int32_t)CDR_E_BAD_INPUT : (int32_t)CDR_OK;
       code = b_id ? (int32_t)CDR_E_VH_LOWER_EVENT_ID : code;
       code = b_ver ? (int32_t)CDR_E_VH_LOWER_VERSION : code;
       code = b_inv ? (int32_t)CDR_P_VH_ITEM_INVALID : code;
 #else
-      const bool newitem = n_vh == 0 || e.ver > vh_last_ver;
+      const uint32_t vh_cap = CP_L.vh_cap;
+      const bool newitem = n_vh == 0 || e.ver > prev_ver;
       const int32_t code = (e.id < 0 || (e.ver < 0 && e.ver != CDR_EMPTY_VERSION)) ? CDR_P_VH_ITEM_INVALID
-                           : (n_vh != 0 && e.ver < vh_last_ver)                     ? CDR_E_VH_LOWER_VERSION
-                           : (n_vh != 0 && e.id <= vh_last_id)                      ? CDR_E_VH_LOWER_EVENT_ID
+                           : (n_vh != 0 && e.ver < prev_ver)                        ? CDR_E_VH_LOWER_VERSION
+                           : (n_vh != 0 && e.id <= prev_id)                         ? CDR_E_VH_LOWER_EVENT_ID
                            : (newitem && n_vh >= vh_cap)                            ? CDR_E_BAD_INPUT
                                                                                     : CDR_OK;
 #endif
       PFAIL(!done && code != CDR_OK, code);
       const bool add = !done && newitem;
       const bool put = add && n_vh != 0;
-      if (put) gput(vh_l + (n_vh - 1), cdr_vh_item{vh_last_id, vh_last_ver});
+      if (put) gput(vh_l + (n_vh - 1), cdr_vh_item{prev_id, prev_ver});
       if (__builtin_amdgcn_ballot_w64(put)) VM_DRAIN();
       n_vh += add ? 1u : 0u;
-      vh_last_ver = SEL(add, e.ver, vh_last_ver);
-      vh_last_id = SEL(done, vh_last_id, e.id);
       }
     }
+    // (a lane the prelude failed keeps the previous event's: nothing reads a failed lane's)
+    prev_id = SEL(done, prev_id, e.id);
+    prev_ver = SEL(done, prev_ver, e.ver);
   };
   // UNI: the row's type_flags word and the one that gates the next loads are the same on every
   // executing lane (stf, stn: scalars), every lane is inside its history, and k + FD - 1 < srows
@@ -591,16 +602,21 @@ k_replay_fast(cdr_launch L) {
       e.aux = mov64(q.aux);
       // the type_flags word first: the loop's uniformity test reads the newest one, and only
       // this step's operand loads are then younger than it
-      t = bld32<CDR_NT_FAST>(S.r, S.l4 + S.col(CDR_COL_TYPE_FLAGS), rowq(k + 2 * FD));
+      // the lane's two element offsets through an opaque copy: the column offset added to a
+      // loop-invariant register would be hoisted out of the loop, one register per column;
+      // added here it folds into the load's immediate offset
+      uint32_t l8 = lane8, l4 = S.l4;
+      asm volatile("" : "+v"(l8), "+v"(l4));
+      t = bld32<CDR_NT_FAST>(S.r, l4 + S.col(CDR_COL_TYPE_FLAGS), rowq(k + 2 * FD));
       const uint32_t so = rowq(k + FD);
       const uint32_t kbn = CDR_FAST_HINT ? (stn & CDR_SEF_KEY_BACK) : 0u, ain = CDR_FAST_HINT ? (stn & CDR_SEF_AUX_IMPL) : 0u;
       q.tf = stn;
 #if CDR_FAST_UNI_SKIP
-#define UNI_LD64(need, c_) ((need) ? bld64<CDR_NT_FAST>(S.r, lane8 + S.col(c_), so) : (int64_t)0)
-#define UNI_LD32(need, c_) ((need) ? bld32<CDR_NT_FAST>(S.r, S.l4 + S.col(c_), so) : 0u)
+#define UNI_LD64(need, c_) ((need) ? bld64<CDR_NT_FAST>(S.r, l8 + S.col(c_), so) : (int64_t)0)
+#define UNI_LD32(need, c_) ((need) ? bld32<CDR_NT_FAST>(S.r, l4 + S.col(c_), so) : 0u)
 #else
-#define UNI_LD64(need, c_) bld64<CDR_NT_FAST>(rs(need), lane8 + S.col(c_), so)
-#define UNI_LD32(need, c_) bld32<CDR_NT_FAST>(rs(need), S.l4 + S.col(c_), so)
+#define UNI_LD64(need, c_) bld64<CDR_NT_FAST>(rs(need), l8 + S.col(c_), so)
+#define UNI_LD32(need, c_) bld32<CDR_NT_FAST>(rs(need), l4 + S.col(c_), so)
 #endif
       q.id = UNI_LD64(!(CDR_FAST_DELTA && (stn & CDR_SEF_ID_NEXT)), CDR_COL_EVENT_ID);
       q.ver = UNI_LD64(!(CDR_FAST_DELTA && (stn & CDR_SEF_VER_SAME)), CDR_COL_VERSION);
@@ -634,7 +650,6 @@ k_replay_fast(cdr_launch L) {
           ld = 0u;
         }
         prev_id = qid;
-        vh_last_id = SEL(isVH, qid, vh_last_id);
       } else {
         general_row(e, k);
       }
@@ -664,7 +679,6 @@ k_replay_fast(cdr_launch L) {
       call_first_k = SEL(bf, k, call_first_k);
       ld = SEL(bf, 0u, ld);
       prev_id = qid;
-      vh_last_id = SEL(isVH, qid, vh_last_id);
     } else
 #endif
     {
@@ -707,7 +721,8 @@ k_replay_fast(cdr_launch L) {
           const bool f = mine && e.key != dsched;
           PFAIL(f, CDR_E_DECISION_NOT_FOUND);
           const bool ok = mine && !f;
-          x_state = SEL(ok && x_state == CDR_STATE_CREATED, (int32_t)CDR_STATE_RUNNING, x_state);
+          static_assert(CDR_STATE_CREATED == 0 && CDR_STATE_RUNNING == 1, "Created -> Running sets bit 0");
+          xs |= (ok && XS_STATE == CDR_STATE_CREATED) ? 1u : 0u;
           dv = SEL(ok, e.ver, dv);
           dstart = SEL(ok, e.id, dstart);
           dreq = SEL(ok, e.h, dreq);
@@ -741,15 +756,14 @@ k_replay_fast(cdr_launch L) {
                 exists |= ((p.flags & CDR_RP_HAS_CHECKSUM) ? p.binary_checksum : 0u) == cks;
               }
             }
-            const uint64_t rc = (uint64_t)Z.ld(0, ZP_RUN_RPCAP);
             const bool app = chk && !exists;
-            const bool f = app && n_rp >= (uint32_t)(rc >> 32);
+            const bool f = app && n_rp >= (app ? CP_L.rp_cap : 0u);
             PFAIL(f, CDR_E_BAD_INPUT);
             const bool put = app && !f;
             if (put) {  // no children / cancels / signals on the fast path: always resettable
               cdr_reset_point p;
               p.binary_checksum = cks;
-              p.run_id = (uint32_t)rc;
+              p.run_id = late(B_.wfs)[w].run_id;
               p.first_decision_completed_id = e.id;
               p.created_time_nano = B_.now_ns;
               p.expiring_time_nano = 0;
@@ -773,11 +787,16 @@ k_replay_fast(cdr_launch L) {
           const int64_t now = B_.now_ns;
           const int64_t na = inc ? datt + 1 : 0;
           const bool tr = na != 0;
+          // CurrentVersion: this event's, or what the closing event left (a closed workflow's stays)
+          const int64_t curv = XS_STATE == CDR_STATE_COMPLETED ? Z.ld(0, ZP_CLOSE_VER) : e.ver;
           dv = SEL(mine, tr ? (isVH ? curv : CDR_EMPTY_VERSION) : CDR_EMPTY_VERSION, dv);
           dsched = SEL(mine, tr ? x_next_event : CDR_EMPTY_EVENT_ID, dsched);
           dstart = SEL(mine, CDR_EMPTY_EVENT_ID, dstart);
           dreq = SEL(mine, EU, dreq);
-          dto = SEL(mine, tr ? x_dt_timeout_value : 0, dto);
+          int32_t dtv = 0;  // ExecutionInfo.DecisionTimeoutValue: the Started event's, from its record
+          if (mine && tr)
+            dtv = ((const GAS cdr_attr_wf_started*)(late(B_.ev.arena) + (uint64_t)bld64(S.r, lane8, S.col(CDR_COL_AUX))))->task_timeout_s;
+          dto = SEL(mine, dtv, dto);
           if (mine) {
             Z.st(0, ZP_DST_TS, 0);
             Z.st(0, ZP_DORIG_TS, 0);
@@ -791,10 +810,10 @@ k_replay_fast(cdr_launch L) {
         case CDR_EV_AT_SCHEDULED: {  // mutableStateBuilder.go:1982-2028
           // CDR_CAP_FAST: the slot is free (one pending activity at most); a second
           // pending one is k_replay's capacity error too (slice_act_slots == 1)
-          const bool f = mine && hw_act != 0 && A.ld(0, AP_SID) != DEAD_KEY;
+          const bool f = mine && XS_ACT && A.ld(0, FP_SID) != DEAD_KEY;
           PFAIL(f, CDR_E_BAD_INPUT);
           const bool ok = mine && !f;
-          hw_act = SEL(ok, 1u, hw_act);
+          xs |= ok ? 0x80000000u : 0u;
           if (ok) {
             const uint32_t aid = (uint32_t)e.key;
             const int32_t s2c = (int32_t)e.h, s2s = e.n;
@@ -802,18 +821,16 @@ k_replay_fast(cdr_launch L) {
             // the activity timer pick over this one activity (timerBuilder.go:211-312):
             // ScheduleToClose unless ScheduleToStart is strictly earlier
             const uint32_t bit = t_s2s < t_s2c ? CDR_TTS_SCHEDULE_TO_START : CDR_TTS_SCHEDULE_TO_CLOSE;
-            A.st(0, AP_SID, e.id);
-            A.st(0, AP_TS2C, t_s2c);
-            A.st(0, AP_TALT, t_s2s);
-            A.st(0, AP_THB, T_NONE);
-            A.st(0, AP_META, (int64_t)(aid | META_FLAG(AF_AIDMAP) | ((uint64_t)bit << META_TTS_SHIFT)));
-            A.st(0, AP_VER, e.ver);
-            A.st(0, AP_STARTED_ID, CDR_EMPTY_EVENT_ID);
-            A.st(0, AP_STARTED_TIME, 0);
-            A.st(0, AP_CANCEL_ID, CDR_EMPTY_EVENT_ID);
-            A.st(0, AP_ROWS, (int64_t)(k | ((uint64_t)call_first_k << 32)));
-            A.st(0, AP_STC_HB, (int64_t)(((uint64_t)e.key >> 32) | ((uint64_t)e.aux & 0xFFFFFFFF00000000ull)));
-            A.st(0, AP_REQ, 0);
+            A.st(0, FP_SID, e.id);
+            A.st(0, FP_TS2C, t_s2c);
+            A.st(0, FP_META, (int64_t)(aid | META_FLAG(AF_AIDMAP) | ((uint64_t)bit << META_TTS_SHIFT)));
+            A.st(0, FP_VER, e.ver);
+            A.st(0, FP_STARTED_ID, CDR_EMPTY_EVENT_ID);
+            A.st(0, FP_STARTED_TIME, 0);
+            A.st(0, FP_CANCEL_ID, CDR_EMPTY_EVENT_ID);
+            A.st(0, FP_ROWS, (int64_t)(k | ((uint64_t)call_first_k << 32)));
+            A.st(0, FP_STC_HB, (int64_t)(((uint64_t)e.key >> 32) | ((uint64_t)e.aux & 0xFFFFFFFF00000000ull)));
+            A.st(0, FP_REQ, 0);
           }
           if constexpr (TASKS) {  // ActivityTask (:265-266), then the pick's ActivityTimeoutTask (:724-729)
             task_x(ok, CDR_TT_ACTIVITY, e.id, t_dom, tlist);
@@ -825,29 +842,27 @@ k_replay_fast(cdr_launch L) {
           break;
         }
         case CDR_EV_AT_STARTED: {  // :2083-2098
-          const bool f = mine && !(hw_act != 0 && A.ld(0, AP_SID) == e.key);
+          const bool f = mine && !(XS_ACT && A.ld(0, FP_SID) == e.key);
           PFAIL(f, CDR_P_ACTIVITY_STARTED_NIL);  // nil deref in Go
           bool t_made = false;  // TASKS: the pick's timer, emitted below in uniform control flow
           int32_t t_tt = 0;
           int64_t t_vis = 0;
           if (mine && !f) {
-            const uint64_t th = (uint64_t)A.ld(0, AP_STC_HB);
+            const uint64_t th = (uint64_t)A.ld(0, FP_STC_HB);
             const int32_t stc = (int32_t)(uint32_t)th, hb = (int32_t)(uint32_t)(th >> 32);
-            const uint64_t m = (uint64_t)A.ld(0, AP_META) | META_FLAG(AF_STARTED);
-            const int64_t t0 = A.ld(0, AP_TS2C);
+            const uint64_t m = (uint64_t)A.ld(0, FP_META) | META_FLAG(AF_STARTED);
+            const int64_t t0 = A.ld(0, FP_TS2C);
             const int64_t ta = e.ts + (int64_t)stc * NS_PER_S;
             const int64_t tb = hb > 0 ? e.ts + (int64_t)hb * NS_PER_S : T_NONE;
             // pick: ScheduleToClose, then StartToClose, then Heartbeat on ties
             const int64_t t1 = ta < t0 ? ta : t0;
             const uint32_t bit =
                 tb < t1 ? CDR_TTS_HEARTBEAT : (ta < t0 ? CDR_TTS_START_TO_CLOSE : CDR_TTS_SCHEDULE_TO_CLOSE);
-            A.st(0, AP_VER, e.ver);
-            A.st(0, AP_STARTED_ID, e.id);
-            A.st(0, AP_REQ, (int64_t)e.h);
-            A.st(0, AP_STARTED_TIME, e.ts);  // LastHeartBeatUpdatedTime = StartedTime
-            A.st(0, AP_TALT, ta);
-            A.st(0, AP_THB, tb);
-            A.st(0, AP_META, (int64_t)(m | ((uint64_t)bit << META_TTS_SHIFT)));
+            A.st(0, FP_VER, e.ver);
+            A.st(0, FP_STARTED_ID, e.id);
+            A.st(0, FP_REQ, (int64_t)e.h);
+            A.st(0, FP_STARTED_TIME, e.ts);  // LastHeartBeatUpdatedTime = StartedTime
+            A.st(0, FP_META, (int64_t)(m | ((uint64_t)bit << META_TTS_SHIFT)));
             if constexpr (TASKS) {  // the pick created a timer unless its status bit was set (timerBuilder.go:211-230)
               t_made = !(m & ((uint64_t)bit << META_TTS_SHIFT));
               t_tt = (int32_t)__builtin_ctz(bit);
@@ -861,24 +876,24 @@ k_replay_fast(cdr_launch L) {
         case CDR_EV_AT_FAILED:
         case CDR_EV_AT_TIMED_OUT:
         case CDR_EV_AT_CANCELED: {
-          const bool live = hw_act != 0 && A.ld(0, AP_SID) == e.key;
+          const bool live = XS_ACT && A.ld(0, FP_SID) == e.key;
           PFAIL(mine && !live, CDR_E_ACTIVITY_NOT_FOUND);
           // the only pending activity holds its own byActivityID entry (another
           // Scheduled with the same ID would need two pending)
           const bool ok = mine && live;
-          PFAIL(ok && !((uint64_t)A.ld(0, AP_META) & META_FLAG(AF_AIDMAP)), CDR_E_ACTIVITY_ID_NOT_FOUND);
-          if (ok) A.st(0, AP_SID, DEAD_KEY);
+          PFAIL(ok && !((uint64_t)A.ld(0, FP_META) & META_FLAG(AF_AIDMAP)), CDR_E_ACTIVITY_ID_NOT_FOUND);
+          if (ok) A.st(0, FP_SID, DEAD_KEY);
           break;
         }
         case CDR_EV_AT_CANCEL_REQUESTED: {  // :2264-2285
-          const uint64_t m = (uint64_t)A.ld(0, AP_META);
-          const bool hit = hw_act != 0 && A.ld(0, AP_SID) != DEAD_KEY && (uint32_t)m == (uint32_t)e.key &&
+          const uint64_t m = (uint64_t)A.ld(0, FP_META);
+          const bool hit = XS_ACT && A.ld(0, FP_SID) != DEAD_KEY && (uint32_t)m == (uint32_t)e.key &&
                            (m & META_FLAG(AF_AIDMAP));
           PFAIL(mine && !hit, CDR_E_MISSING_ACTIVITY_INFO);
           if (mine && hit) {
-            A.st(0, AP_VER, e.ver);
-            A.st(0, AP_META, (int64_t)(m | META_FLAG(AF_CANCEL)));
-            A.st(0, AP_CANCEL_ID, e.id);
+            A.st(0, FP_VER, e.ver);
+            A.st(0, FP_META, (int64_t)(m | META_FLAG(AF_CANCEL)));
+            A.st(0, FP_CANCEL_ID, e.id);
           }
           break;
         }
@@ -902,12 +917,14 @@ k_replay_fast(cdr_launch L) {
                          : ut == CDR_EV_WF_TIMED_OUT ? CDR_CLOSE_TIMED_OUT
                          : ut == CDR_EV_WF_CANCELED  ? CDR_CLOSE_CANCELED
                                                      : CDR_CLOSE_TERMINATED;
-          const bool f = mine && !transition_ok(x_state, x_close, CDR_STATE_COMPLETED, cs);
+          const bool f = mine && !transition_ok(XS_STATE, XS_CLOSE, CDR_STATE_COMPLETED, cs);
           PFAIL(f, CDR_E_INVALID_STATE_TRANSITION);
           const bool ok = mine && !f;
-          x_state = SEL(ok, (int32_t)CDR_STATE_COMPLETED, x_state);
-          x_close = SEL(ok, (int32_t)cs, x_close);
-          if (ok) Z.st(0, ZP_COMPLETION_BATCH, call_first_id);
+          xs = SEL(ok, (xs & 0x80000000u) | (uint32_t)CDR_STATE_COMPLETED | ((uint32_t)cs << 8), xs);
+          if (ok) {
+            Z.st(0, ZP_COMPLETION_BATCH, call_first_id);
+            Z.st(0, ZP_CLOSE_VER, e.ver);
+          }
           // appendTasksForFinishedExecutions (:775-787)
           task_x(ok, CDR_TT_CLOSE_EXECUTION, 0, 0, 0);
           task_t(ok, CDR_TT_DELETE_HISTORY, 0, 0, e.ts + (int64_t)D.retention_days * 86400ll * NS_PER_S);
@@ -971,6 +988,8 @@ k_replay_fast(cdr_launch L) {
 #undef SEL
 #undef FLD_CAPTURE
   if constexpr (TASKS && CDR_FAST_TBUF > 0) tq_flush();
+  // the failed event's id from its row (row 0 of an empty history is out of range: 0)
+  int64_t err_id = err != CDR_OK ? bld64(S.r, el8(err_k, len, lane), S.col(CDR_COL_EVENT_ID)) : 0;
   if (len > 0 && err == CDR_OK) x_next_event = prev_id + 1;
   if (err == CDR_OK && D.parent < 0 && D.expected_next_event_id != 0 && x_next_event != D.expected_next_event_id) {
     err = CDR_E_REBUILD_NEXT_EVENT_ID;  // nDCStateRebuilder.go:139-143
@@ -983,7 +1002,14 @@ k_replay_fast(cdr_launch L) {
     err_k = len;
   }
   const bool ok = err == CDR_OK;
-  const bool act_live = ok && hw_act != 0 && A.ld(0, AP_SID) != DEAD_KEY;
+  uint32_t n_sa = 0;  // the Started event's search attributes, as its block stored them
+  if (ok) {
+    const GAS cdr_attr_wf_started* a =
+        gp((const cdr_attr_wf_started*)(B_.ev.arena + (uint64_t)bld64(S.r, lane8, S.col(CDR_COL_AUX))));
+    const uint32_t cnt = a->search_attr_len, cap = CP.sa_cap;
+    n_sa = (a->flags & CDR_SF_HAS_SEARCH_ATTR) ? (cnt < cap ? cnt : cap) : 0u;
+  }
+  const bool act_live = ok && XS_ACT && A.ld(0, FP_SID) != DEAD_KEY;
   cdr_wf_result r;
   r.code = err;
   r.flags = D.parent >= 0 ? CDR_RF_IS_NEWRUN : 0u;
@@ -1005,25 +1031,25 @@ k_replay_fast(cdr_launch L) {
       ld_rec(ld, dv, dsched, dstart, dreq, dto, datt, Z.ld(0, ZP_DSC_TS), Z.ld(0, ZP_DST_TS), Z.ld(0, ZP_DORIG_TS));
   cdr_activity_info o{};
   if (act_live) {  // the pending activity as a persisted row (as in k_replay)
-    const uint64_t rows = (uint64_t)A.ld(0, AP_ROWS);
+    const uint64_t rows = (uint64_t)A.ld(0, FP_ROWS);
     const uint32_t o_s = el8((uint32_t)rows, len, lane), o_b = el8((uint32_t)(rows >> 32), len, lane);
     const int64_t sched_ts = bld64(S.r, o_s, S.col(CDR_COL_TIMESTAMP));
     const uint32_t arec = (uint32_t)bld64(S.r, o_s, S.col(CDR_COL_AUX));
     const GAS cdr_attr_at_scheduled* a = gp((const cdr_attr_at_scheduled*)(B_.ev.arena + arec));
-    const uint64_t m = (uint64_t)A.ld(0, AP_META);
+    const uint64_t m = (uint64_t)A.ld(0, FP_META);
     const bool retry = (a->flags & CDR_AF_HAS_RETRY) != 0;
     const int32_t s2c = a->s2c_s, xs = a->retry_expiration_s;
-    o.version = A.ld(0, AP_VER);
-    o.schedule_id = A.ld(0, AP_SID);
+    o.version = A.ld(0, FP_VER);
+    o.schedule_id = A.ld(0, FP_SID);
     o.scheduled_event_batch_id = bld64(S.r, o_b, S.col(CDR_COL_EVENT_ID));
     o.scheduled_time = sched_ts;
-    o.started_id = A.ld(0, AP_STARTED_ID);
-    o.started_time = A.ld(0, AP_STARTED_TIME);
-    o.last_heartbeat_time = A.ld(0, AP_STARTED_TIME);
+    o.started_id = A.ld(0, FP_STARTED_ID);
+    o.started_time = A.ld(0, FP_STARTED_TIME);
+    o.last_heartbeat_time = A.ld(0, FP_STARTED_TIME);
     o.expiration_time = sched_ts + (int64_t)((retry && xs > s2c) ? xs : s2c) * NS_PER_S;
-    o.cancel_request_id = A.ld(0, AP_CANCEL_ID);
+    o.cancel_request_id = A.ld(0, FP_CANCEL_ID);
     o.activity_id = (uint32_t)m;
-    o.request_id = (uint32_t)A.ld(0, AP_REQ);
+    o.request_id = (uint32_t)A.ld(0, FP_REQ);
     o.task_list = a->task_list;
     o.nonretriable = retry ? a->nonretriable : 0u;
     o.s2s = a->s2s_s;
@@ -1048,8 +1074,8 @@ k_replay_fast(cdr_launch L) {
     hv[0] = dreq;  // decision_request_id, flags
     hv[1] = x_flags;
     p64(2, Z.ld(0, ZP_COMPLETION_BATCH));
-    hv[4] = (uint32_t)x_state;
-    hv[5] = (uint32_t)x_close;
+    hv[4] = (uint32_t)XS_STATE;
+    hv[5] = (uint32_t)XS_CLOSE;
     p64(6, call_first_id);  // last_first_event_id: stateBuilder.go:603 of the last call
     p64(8, bld64(S.r, el8(len - 1, len, lane), S.col(CDR_COL_TASK_ID)));  // last_event_task_id :155
     p64(10, x_next_event);
@@ -1067,7 +1093,7 @@ k_replay_fast(cdr_launch L) {
     hv[31] = n_sa;
   }
   const bool vh_on = ok && n_vh;
-  const cdr_vh_item vi{vh_last_id, vh_last_ver};
+  const cdr_vh_item vi{prev_id, prev_ver};
   GAS cdr_vh_item* const vh_dst = vh_on ? vh + (n_vh - 1) : nullptr;
   GAS cdr_activity_info* const act_dst = act_live ? gp(O_.act) + CP.act_off : nullptr;
   coop_put<7>(gp(O_.result) + w, r, true, 0);
@@ -1082,6 +1108,8 @@ k_replay_fast(cdr_launch L) {
   {
     constexpr uint32_t RS = 65;  // LDS row stride (dwords): conflict-free column writes
     static_assert(33u * RS * 4u <= FAST_LDS_BYTES, "the transpose fits the planes it reuses");
+    static_assert(11u * RS * 8u <= FAST_LDS_BYTES, "so does coop_put<10>'s");
+    static_assert(16u * FAST_LDS_BYTES <= 160u * 1024u, "sixteen one-wave workgroups per CU: four waves per SIMD");
     uint32_t* const L32 = (uint32_t*)cdr_lds;
     const uint64_t em = __builtin_amdgcn_read_exec();
     const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(em >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)em, 0u));
@@ -1113,6 +1141,10 @@ k_replay_fast(cdr_launch L) {
 #undef vh
 #undef rp
 #undef vh_l
+#undef XS_STATE
+#undef XS_CLOSE
+#undef XS_ACT
+#undef CP_L
 #undef rp_l
 #undef sa
 #undef B_
