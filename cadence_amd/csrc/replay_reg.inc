@@ -728,8 +728,19 @@ __device__ __forceinline__ void reg_slice(const uint32_t s) {
         const uint32_t b = (bi >> 4) & 0xFu;
         const bool made = best >= 0 && !((bi >> 8) & b);
         RSET(a_inf, NA, made ? best : -1, bi | (b << 8));
-        // ActivityTimeoutTask (timerBuilder.go:391-408): TimerTaskStatus bit -> shared.TimeoutType
-        task_t(made, CDR_TT_ACTIVITY_TIMEOUT, (int32_t)__builtin_ctz(b | 16u), (int64_t)bs, bt, 0);
+        // ActivityTimeoutTask (timerBuilder.go:391-408): TimerTaskStatus bit -> shared.TimeoutType.
+        // Attempt is the row's (timerBuilder.go:263-302, 404): 0 for an activity this replay
+        // scheduled, the loaded row's for a carried one — the head of a pick can be a loaded
+        // activity whatever event asked for the pick (as the general kernel's act_task)
+        int64_t att = 0;
+        if constexpr (CARRY && TASKS) {
+          if (made && ((a_cy >> best) & 1u)) {
+            const GAS cdr_carry* CY = gp(B_.carry);
+            att = gget(gp(CY->state.act) + gget(gp(CY->caps) + csrc).act_off +
+                       rl(RA0 + RA_W * (uint32_t)best + 4, lane)).attempt;
+          }
+        }
+        task_t(made, CDR_TT_ACTIVITY_TIMEOUT, (int32_t)__builtin_ctz(b | 16u), (int64_t)bs, bt, att);
       }
     }
     // ---- user timers (:324-350 -> :2877-2991)

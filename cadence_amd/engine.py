@@ -968,6 +968,7 @@ _HANDLE_FIELDS = {
     "parent_run_id", "task_list", "workflow_type", "decision_request_id", "cron_schedule", "memo", "nonretriable",
     "branch_tree_id", "activity_id", "request_id", "timer_id", "started_workflow_id", "started_run_id",
     "domain_name", "signal_name", "input", "control", "binary_checksum", "key", "value",
+    "target_workflow_id", "target_run_id",  # cdr_task
 }
 
 

@@ -343,8 +343,11 @@ def test_oracle_carry_in_onto_hand_set_rows():
 
 # ====================================================================== routes: what the planner gives to whom
 # Cases whose local / NDC instances the planner keeps off the fast-path kernel, with the reason
-TWO_LIVE = ["act_close_completed", "act_close_failed", "act_close_timedout", "act_close_canceled"]
-NOT_FAST_TYPES = ["timer_started", "timer_fired_repick", "timer_canceled_repick", "child_initiated", "child_started",
+TWO_LIVE = ["act_close_completed", "act_close_failed", "act_close_timedout", "act_close_canceled",
+            "act_close_completed_picks", "act_close_failed_picks", "act_close_timedout_picks",
+            "act_close_canceled_picks", "act_exact_ties"]
+NOT_FAST_TYPES = ["timer_started", "timer_fired_repick", "timer_canceled_repick", "timer_repick_created_head_then_none",
+                  "timer_expiry_tie", "ext_own_domain", "child_initiated", "child_started",
                   "child_removed_start_failed", "child_removed_completed", "child_removed_failed",
                   "child_removed_canceled", "child_removed_timedout", "child_removed_terminated", "cancel_initiated",
                   "cancel_initiated_child_only", "cancel_failed", "cancel_delivered", "signal_initiated",
